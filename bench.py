@@ -13,7 +13,12 @@ the per-episode times (HIP events between steps).  Inputs: synthetic reset state
 (Philox), weights data/models/experiment_GoTo-seed_0.pth (committed fixture), replay
 pre-filled with 100 acting ticks.  Each episode's 100 ticks replay one captured hipGraph.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds,
+after the timed region, everything else the line can report: per-kernel durations and the
+roofline, the acting-only rollouts, the CPU baselines (and at N > 1 the second timed region
+over RCCL).  --dump-outputs DIR writes what the last timed step left a caller (dump_outputs).
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
        N > 1 under a launcher (torch.distributed.run --nproc-per-node N ... bench.py --gpus N): one
        rank per process as the launcher started them.  N > 1 without one (WORLD_SIZE unset): this
        process starts the N ranks itself (a torch.distributed.run child, before any GPU call), relays
@@ -119,6 +124,12 @@ def parse():
                     help="gat3: the Flocking checkpoints' three-layer GAT (acting only, --mode act)")
     ap.add_argument("--batch", type=int, default=None, help="sampled graphs per update per GPU (default = envs)")
     ap.add_argument("--no-graph", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure the per-kernel durations and roofline, the "
+                         "acting-only rollouts and the CPU baselines (N > 1: the RCCL timed region as well)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step left (state, per-tick outputs, learner) as "
+                         "DIR/<name>.npy, float32")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true")
@@ -376,10 +387,12 @@ def main():
         return elapsed, spread, graph
 
     elapsed, tick_spread, graph = timed_region()
-    # N > 1 with the peer exchange: the same workload again with the RCCL all-reduce after the
+    if args.dump_outputs:   # before anything below touches the engine again
+        dump_outputs(args.dump_outputs, train_outputs(eng), rank, world)
+    # --full, N > 1 with the peer exchange: the same workload again with the RCCL all-reduce after the
     # slab reduce (north_star's "single RCCL all-reduce over xGMI"), so one run reports both paths
     both = None
-    if distributed and peer is not None and args.backend == "nccl" and args.compare_rccl:
+    if args.full and distributed and peer is not None and args.backend == "nccl" and args.compare_rccl:
         peer.check()
         el_peer = elapsed
         eng.peer = None
@@ -430,7 +443,7 @@ def main():
     #      timed region's per-episode reset.  3-launch tick: each kernel's chain (TD and the slab
     #      reduce are pure functions of their inputs).
     kt = {}
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         stream = torch.cuda.current_stream()
 
         def chain_us(fn, kchain=50):
@@ -463,7 +476,7 @@ def main():
                              ("grad_reduce_kernel", eng.launch_grad_reduce)):
                 kt[name] = chain_us(fn)
 
-    d = mean_in_degree(args, eng)
+    d = mean_in_degree(args, eng) if kt else 0.0   # the roofline's FLOP counts only
     if args.conv == "gat":
         td_flops_launch = S * N * (2 * gat_fwd_flops(N, d) + td_bwd_flops(N, d))
     else:
@@ -511,7 +524,7 @@ def main():
     # recorded evaluations ran k = 5, data/test_stats); the training graph (this engine's) is
     # reported beside it, labelled
     acting = None
-    if world == 1:
+    if args.full and world == 1:
         import swarm_amd
         k_eval = min(10, N) if N >= 10 else min(5, N)
         e_knn = swarm_amd.SwarmEngine(scen, N, B, seed=0, params=w0, graph="knn", knn_k=k_eval, conv=args.conv,
@@ -525,7 +538,7 @@ def main():
                                     "graph's rollout, which is acting_only.training_graph")
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline_leg(args, w0, scen, B, N, S, eng)
 
     if rank == 0:
@@ -551,6 +564,39 @@ def main():
         print(json.dumps(line))
     if distributed:
         torch.distributed.destroy_process_group()
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def train_outputs(eng) -> dict:
+    """What the last training tick left a caller of the engine: the env state, the tick's
+    reward / mean goal distance / hits, the learner (the weights in use and the set the pending
+    optimizer step writes, the Adam moments, the target, the reduced gradient with its loss
+    sum) and the control block's loss and gradient norm.  Read as they stand (no flush)."""
+    out = {"state": eng.state, "reward": eng.reward, "avg_dist": eng.avg_dist, "hits": eng.hits,
+           "params": eng.params, "params_next": eng.w_nxt, "adam_m": eng.adam_m, "adam_m_next": eng.m_nxt,
+           "adam_v": eng.adam_v, "adam_v_next": eng.v_nxt, "target": eng.target, "grad": eng.grad,
+           "loss_gradnorm": eng.ctrl.view(torch.float32)[5:7]}
+    if eng.scenario_state is not None:
+        out["scenario_state"] = eng.scenario_state
+    return out
+
+
+def dump_outputs(where: str, arrays: dict, rank: int = 0, world: int = 1) -> None:
+    """Write each array as where/<name>.npy (float32; rank r > 0 of several: <name>.rank<r>.npy).
+    All files together stay under DUMP_BUDGET_BYTES: an array above its equal share of the budget
+    is written as a fixed sample of its flattened elements (sorted indices from a generator seeded
+    with 0, so two runs with the same arguments sample the same elements).  Called after the timed
+    region's synchronize; the copies to the host wait for anything still queued."""
+    os.makedirs(where, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // (max(1, len(arrays)) * world) // 4 - 64   # elements per file, header allowed for
+    for name, t in arrays.items():
+        a = np.ascontiguousarray(t.detach().to("cpu", torch.float32).numpy())
+        if a.size > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(where, name + ("" if rank == 0 else f".rank{rank}") + ".npy"), a)
 
 
 def lib_identity() -> dict:
@@ -756,16 +802,18 @@ def bench_act(args, eng, world, rank, distributed, max_steps):
     B, N = args.envs, args.agents
 
     def run(n_episodes):   # one step = one episode: reset, then one max_steps-tick rollout launch
+        res = None
         for i in range(n_episodes):
             eng.reset()
-            eng.rollout(max_steps, tick0=i * max_steps, eps=0.0)
+            res = eng.rollout(max_steps, tick0=i * max_steps, eps=0.0)
+        return res
 
     run(args.warmup)
     torch.cuda.synchronize()
     if distributed:
         torch.distributed.barrier()
     t0 = time.perf_counter()
-    run(args.steps)
+    last = run(args.steps)
     torch.cuda.synchronize()
     if distributed:
         torch.distributed.barrier()
@@ -774,8 +822,10 @@ def bench_act(args, eng, world, rank, distributed, max_steps):
         t = torch.tensor([elapsed], device="cuda", dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs:   # the last timed rollout's results and the state it left
+        dump_outputs(args.dump_outputs, {"state": eng.state, **(last or {})}, rank, world)
     roof = None
-    if not args.no_kernel_timing:   # one 100-tick rollout launch, HIP events on its stream
+    if args.full and not args.no_kernel_timing:   # one 100-tick rollout launch, HIP events on its stream
         roof = rollout_roofline(args, eng, max_steps, acting_fnode(args, eng))
     if rank == 0:
         g = {"complete": "complete", "knn": f"kNN-{args.knn_k}", "radius": f"radius-{args.radius}"}[args.graph]

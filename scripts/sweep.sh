@@ -1,8 +1,10 @@
 #!/bin/bash
+# the headline line at 40 steps, then tools/sweep.py's configurations; logs go to $OUT (default: bench_out/)
 export TMPDIR=/tmp
-mkdir -p gpurun_out
-timeout -k 10 300 python bench.py --steps 40 --warmup 3 --no-cpu-baseline > gpurun_out/bench_head.log 2>&1
-rc=$?; echo "bench rc=$rc"; tail -1 gpurun_out/bench_head.log
+OUT=${OUT:-bench_out}
+mkdir -p $OUT
+timeout -k 10 300 python bench.py --full --steps 40 --warmup 3 --no-cpu-baseline > $OUT/bench_head.log 2>&1
+rc=$?; echo "bench rc=$rc"; tail -1 $OUT/bench_head.log
 if [ $rc -ne 0 ]; then exit $rc; fi
-timeout -k 10 1000 python -u tools/sweep.py gpurun_out/sweep.jsonl > gpurun_out/sweep.log 2>&1
-rc=$?; cat gpurun_out/sweep.log | tail -25; exit $rc
+timeout -k 10 1000 python -u tools/sweep.py $OUT/sweep.jsonl > $OUT/sweep.log 2>&1
+rc=$?; cat $OUT/sweep.log | tail -25; exit $rc

@@ -57,7 +57,10 @@ def golden_weights():
 @pytest.fixture(scope="session")
 def trajectories():
     import numpy as np
-    return np.load(os.path.join(GOLDEN, "trajectories.npz"))
+    out = {}   # one file per scenario (each stays under the 1 MiB limit for committed files)
+    for scen in ("go_to", "obstacle_avoidance"):
+        out.update(np.load(os.path.join(GOLDEN, f"trajectories_{scen}.npz")))
+    return out
 
 
 def fp32_ulp(b):

@@ -98,7 +98,9 @@ def main():
                     traj[key + "/dist"] = dist[:, 1].astype(np.float64)
                     traj[key + "/hits"] = dist[:, 2].astype(np.float64)
                     traj[key + "/ref_action"] = ref_actions(P, sid)
-    np.savez_compressed(os.path.join(HERE, "trajectories.npz"), **traj)
+    for scen, _, _ in SCEN:   # one file per scenario: each stays under 1 MiB
+        np.savez_compressed(os.path.join(HERE, f"trajectories_{scen}.npz"),
+                            **{k: v for k, v in traj.items() if k.startswith(scen + "/")})
 
     # topk tie vectors: grid-like rows with exact ties
     rng = np.random.default_rng(1234)

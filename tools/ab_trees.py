@@ -7,7 +7,8 @@ own time limit, and appends one JSON line per run to the output file: the varian
 the whole-step rate, the per-tick spread and the per-kernel chain periods of the bench line.
 
 usage: python tools/ab_trees.py OUT.jsonl ROUNDS VARIANT[,VARIANT...] [bench args...]
-       e.g. python tools/ab_trees.py gpurun_out/ab.jsonl 3 abx/base,. --steps 40 --no-cpu-baseline
+       e.g. python tools/ab_trees.py ab.jsonl 3 abx/base,. --steps 40 --full --no-cpu-baseline
+       (--full for the per-kernel chain periods; trees from before that option take no --full)
 """
 import json
 import os
