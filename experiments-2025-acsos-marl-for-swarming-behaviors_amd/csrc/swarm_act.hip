@@ -7,7 +7,7 @@
 //   go_to_position_scenario.py:83-132, obstacle_avoidance_scenario.py:94-173
 #include <stdlib.h>
 
-#include "swarm_actk.h"
+#include "swarm_launch.h"
 
 namespace swarm {
 
@@ -21,22 +21,6 @@ __global__ __launch_bounds__(64 * kActWPB) void act_kernel(const swarm_ctrl* __r
   __shared__ ActSmem<NS> S;
   act_body<NS, MODE, SCEN, SPEC, false, NET>(S, blockIdx.x, gridDim.x, ctrl, state, grad, w_cur, m_cur, v_cur, B, N, A);
 }
-
-// A/B knob: SWARM_ROLLOUT_WPE = w > 0 launches the multi-tick rollouts through this copy of the
-// kernel with an occupancy target of w waves per SIMD (the register budget the compiler may
-// use); 0 = act_kernel with the compiler's default
-#ifndef SWARM_ROLLOUT_WPE
-#define SWARM_ROLLOUT_WPE 0
-#endif
-#if SWARM_ROLLOUT_WPE > 0
-template <int NS, int MODE, int SCEN, int SPEC, int NET = SWARM_NET_GCN>
-__global__ __launch_bounds__(64 * kActWPB) __attribute__((amdgpu_waves_per_eu(SWARM_ROLLOUT_WPE, SWARM_ROLLOUT_WPE)))
-void act_kernel_w(const swarm_ctrl* __restrict__ ctrl, float* state, const float* grad, const float* w_cur,
-                  const float* m_cur, const float* v_cur, int B, int N, ActArgs A) {
-  __shared__ ActSmem<NS> S;
-  act_body<NS, MODE, SCEN, SPEC, false, NET>(S, blockIdx.x, gridDim.x, ctrl, state, grad, w_cur, m_cur, v_cur, B, N, A);
-}
-#endif
 
 // ---------------------------------------------------------------- reset
 // reset_world_at + generate_grid; centre from Philox + Box-Muller (fp32 libm)
@@ -146,97 +130,24 @@ using namespace swarm;
 
 namespace {
 
-int check_cfg(const swarm_config* c) {
-  if (!c || c->n_envs < 0 || c->n_agents < 1 || c->n_agents > 32) return SWARM_E_BADARG;
-  if (c->scenario != SWARM_GOTO && c->scenario != SWARM_OBSTACLE_AVOIDANCE && c->scenario != SWARM_FLOCKING)
-    return SWARM_E_BADARG;
-  if (c->scenario == SWARM_FLOCKING && c->n_agents < 2) return SWARM_E_BADARG;   // mean over the other agents
-  if (c->net != SWARM_NET_GCN && (c->net != SWARM_NET_GAT3 || c->conv != SWARM_CONV_GAT)) return SWARM_E_BADARG;
-  if (c->graph < 0 || c->graph > 3 || (c->conv != SWARM_CONV_GAT && c->conv != SWARM_CONV_GCN)) return SWARM_E_BADARG;
-  if (c->graph == SWARM_GRAPH_KNN && (c->knn_k < 1 || c->knn_k > c->n_agents)) return SWARM_E_KNN_K;
-  if (c->graph == SWARM_GRAPH_RADIUS && !(c->radius > 0.0f)) return SWARM_E_BADARG;
-  return 0;
-}
+int check_cfg(const swarm_config* c) { return check_config(c, kCfgAct); }
 
-ActArgs make_args(const swarm_config* c) {
-  ActArgs a = {};
-  a.B = c->n_envs; a.N = c->n_agents; a.scenario = c->scenario; a.graph = c->graph;
-  a.k = c->knn_k; a.conv = c->conv; a.env_offset = c->env_offset; a.flags = c->flags;
-  a.k0 = (uint32_t)(c->seed & 0xFFFFFFFFu); a.k1 = (uint32_t)(c->seed >> 32);
-  a.radius = c->radius;
-  a.net = c->net;
-  return a;
-}
-
-int n_tiles(const swarm_config* c) { return c->n_envs; }   // one wave per environment
-
+// one wave per environment, kActWPB environments per block; which act_kernel: ActSpecs (swarm_launch.h)
 template <int MODE>
-int launch_act(const ActArgs& a, int tiles, hipStream_t st) {
-  if (tiles == 0) return 0;
-  const dim3 grid((tiles + kActWPB - 1) / kActWPB), block(64 * kActWPB);
-  const float *g = a.lr.grad, *w = a.lr.w_cur, *m = a.lr.m_cur, *v = a.lr.v_cur;
-  // specialised kernels for the training tick (complete graph, GAT or GCN) and the rollout
-  // (those two plus kNN + GAT, the Simulator's graph, and GoTo's radius + GAT, the north_star
-  // graph); everything else runs SPEC_RUNTIME
-  constexpr bool kTick = MODE == MODE_TICK || MODE == MODE_ROLLOUT;
-  constexpr int S1 = kTick ? SPEC_COMPLETE_GAT : SPEC_RUNTIME;
-  constexpr int S2 = kTick ? SPEC_COMPLETE_GCN : SPEC_RUNTIME;
-  constexpr int S3 = MODE == MODE_ROLLOUT ? SPEC_KNN_GAT : SPEC_RUNTIME;
-  constexpr int S4 = MODE == MODE_ROLLOUT ? SPEC_RADIUS_GAT : SPEC_RUNTIME;   // GoTo, N <= 8 only
-  const int spec = kTick ? spec_of(a.graph, a.conv) : SPEC_RUNTIME;
-#if SWARM_ROLLOUT_WPE > 0
-#define SWARM_ACT_LAUNCH1(NS, SC, SP)                                                                               \
-  do {                                                                                                              \
-    if constexpr (MODE == MODE_ROLLOUT)                                                                             \
-      hipLaunchKernelGGL((act_kernel_w<NS, MODE, SC, SP>), grid, block, 0, st, a.ctrl, a.state, g, w, m, v, a.B, a.N, a); \
-    else                                                                                                            \
-      hipLaunchKernelGGL((act_kernel<NS, MODE, SC, SP>), grid, block, 0, st, a.ctrl, a.state, g, w, m, v, a.B, a.N, a); \
-  } while (0)
-#else
-#define SWARM_ACT_LAUNCH1(NS, SC, SP) \
-  hipLaunchKernelGGL((act_kernel<NS, MODE, SC, SP>), grid, block, 0, st, a.ctrl, a.state, g, w, m, v, a.B, a.N, a)
-#endif
-#define SWARM_ACT_LAUNCH(NS, SC)                                  \
-  do {                                                            \
-    if (spec == SPEC_COMPLETE_GAT) SWARM_ACT_LAUNCH1(NS, SC, S1);  \
-    else if (spec == SPEC_COMPLETE_GCN) SWARM_ACT_LAUNCH1(NS, SC, S2); \
-    else if (spec == SPEC_KNN_GAT) SWARM_ACT_LAUNCH1(NS, SC, S3);  \
-    else SWARM_ACT_LAUNCH1(NS, SC, SPEC_RUNTIME);                  \
-  } while (0)
-  constexpr int OA = (MODE == MODE_Q) ? SWARM_GOTO : SWARM_OBSTACLE_AVOIDANCE;   // MODE_Q has no physics
-  constexpr int FL = (MODE == MODE_Q) ? SWARM_GOTO : SWARM_FLOCKING;
-  const bool oa = MODE != MODE_Q && a.scenario == SWARM_OBSTACLE_AVOIDANCE;
-  const bool fl = MODE != MODE_Q && a.scenario == SWARM_FLOCKING;   // flocking: runtime graph/conv only
-  if constexpr (MODE != MODE_STEP) {
-  if (a.net == SWARM_NET_GAT3) {   // three-layer GAT (forward only): runtime graph
-#define SWARM_ACT_LAUNCH3(NS)                                                                                   \
-  do {                                                                                                          \
-    if (fl) hipLaunchKernelGGL((act_kernel<NS, MODE, FL, SPEC_RUNTIME, SWARM_NET_GAT3>), grid, block, 0, st,   \
-                               a.ctrl, a.state, g, w, m, v, a.B, a.N, a);                                      \
-    else if (oa) hipLaunchKernelGGL((act_kernel<NS, MODE, OA, SPEC_RUNTIME, SWARM_NET_GAT3>), grid, block, 0, \
-                                    st, a.ctrl, a.state, g, w, m, v, a.B, a.N, a);                             \
-    else hipLaunchKernelGGL((act_kernel<NS, MODE, SWARM_GOTO, SPEC_RUNTIME, SWARM_NET_GAT3>), grid, block, 0, \
-                            st, a.ctrl, a.state, g, w, m, v, a.B, a.N, a);                                     \
-  } while (0)
-    if (a.N <= 8) SWARM_ACT_LAUNCH3(8);
-    else if (a.N <= 16) SWARM_ACT_LAUNCH3(16);
-    else SWARM_ACT_LAUNCH3(32);
-#undef SWARM_ACT_LAUNCH3
-    return (int)hipGetLastError();
-  }
-  }
-  if (a.N <= 8) {
-    if (fl) SWARM_ACT_LAUNCH1(8, FL, SPEC_RUNTIME);
-    else if (oa) SWARM_ACT_LAUNCH(8, OA);
-    else if (spec == SPEC_RADIUS_GAT) SWARM_ACT_LAUNCH1(8, SWARM_GOTO, S4);
-    else SWARM_ACT_LAUNCH(8, SWARM_GOTO);
-  } else if (a.N <= 16) {
-    if (fl) SWARM_ACT_LAUNCH1(16, FL, SPEC_RUNTIME); else if (oa) SWARM_ACT_LAUNCH(16, OA); else SWARM_ACT_LAUNCH(16, SWARM_GOTO);
-  } else {
-    if (fl) SWARM_ACT_LAUNCH1(32, FL, SPEC_RUNTIME); else if (oa) SWARM_ACT_LAUNCH(32, OA); else SWARM_ACT_LAUNCH(32, SWARM_GOTO);
-  }
-#undef SWARM_ACT_LAUNCH
-#undef SWARM_ACT_LAUNCH1
+int launch_act(const ActArgs& a, hipStream_t st) {
+  if (a.B == 0) return 0;
+  const dim3 grid((a.B + kActWPB - 1) / kActWPB), block(64 * kActWPB);
+  with_slots<8, 16, 32>(a.N, [&](auto ns) {
+    with_scenario<MODE != MODE_Q>(a.scenario, [&](auto sc) {
+      with_net<MODE != MODE_STEP>(a.net, [&](auto net) {
+        constexpr int NS = decltype(ns)::value, SC = decltype(sc)::value, NET = decltype(net)::value;
+        with_spec<ActSpecs<NS, MODE, SC, NET>>(a.graph, a.conv, [&](auto sp) {
+          hipLaunchKernelGGL((act_kernel<NS, MODE, SC, decltype(sp)::value, NET>), grid, block, 0, st, a.ctrl, a.state,
+                             a.lr.grad, a.lr.w_cur, a.lr.m_cur, a.lr.v_cur, a.B, a.N, a);
+        });
+      });
+    });
+  });
   return (int)hipGetLastError();
 }
 
@@ -277,8 +188,8 @@ int swarm_env_reset(const swarm_config* cfg, float* state, uint32_t episode, voi
   const int n = cfg->n_envs * cfg->n_agents;
   if (n == 0) return 0;
   hipLaunchKernelGGL(reset_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, cfg->n_envs,
-                     cfg->n_agents, cfg->scenario, cfg->flags, (uint32_t)(cfg->seed & 0xFFFFFFFFu),
-                     (uint32_t)(cfg->seed >> 32), cfg->env_offset, episode, state);
+                     cfg->n_agents, cfg->scenario, cfg->flags, seed_k0(cfg), seed_k1(cfg), cfg->env_offset, episode,
+                     state);
   if (cfg->scenario == SWARM_FLOCKING)
     hipLaunchKernelGGL(flock_state_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, cfg->n_envs,
                        cfg->n_agents, 1, state);
@@ -304,23 +215,20 @@ int swarm_env_step(const swarm_config* cfg, float* state, const int32_t* actions
                    void* stream) {
   if (int e = check_cfg(cfg)) return e;
   if (!actions) return SWARM_E_BADARG;
-  ActArgs a = make_args(cfg);
+  ActArgs a = make_act_args(cfg);
   a.state = state; a.actions = actions;
   if (out) { a.out = *out; a.out.q = nullptr; a.out.mult = nullptr; }
-  return launch_act<MODE_STEP>(a, n_tiles(cfg), (hipStream_t)stream);
+  return launch_act<MODE_STEP>(a, (hipStream_t)stream);
 }
 
 int swarm_build_graph(const swarm_config* cfg, const float* x, uint8_t* mult, void* stream) {
-  if (int e = check_cfg(cfg)) return e;
-  if (cfg->graph == SWARM_GRAPH_DENSE) return SWARM_E_BADARG;
-  ActArgs a = make_args(cfg);
+  if (int e = check_config(cfg, kCfgActGraph)) return e;
+  ActArgs a = make_act_args(cfg);
   a.x = x;
-  const int tiles = n_tiles(cfg);
-  if (tiles == 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
-  if (a.N <= 8) hipLaunchKernelGGL((graph_kernel<8>), dim3(tiles), dim3(64), 0, st, a, mult);
-  else if (a.N <= 16) hipLaunchKernelGGL((graph_kernel<16>), dim3(tiles), dim3(64), 0, st, a, mult);
-  else hipLaunchKernelGGL((graph_kernel<32>), dim3(tiles), dim3(64), 0, st, a, mult);
+  if (a.B == 0) return 0;
+  with_slots<8, 16, 32>(a.N, [&](auto ns) {   // one wave per environment
+    hipLaunchKernelGGL((graph_kernel<decltype(ns)::value>), dim3(a.B), dim3(64), 0, (hipStream_t)stream, a, mult);
+  });
   return (int)hipGetLastError();
 }
 
@@ -342,46 +250,45 @@ int swarm_q_forward(const swarm_config* cfg, const float* params, const float* x
                     void* stream) {
   if (int e = check_cfg(cfg)) return e;
   if (cfg->graph == SWARM_GRAPH_DENSE && !mult) return SWARM_E_BADARG;
-  ActArgs a = make_args(cfg);
+  ActArgs a = make_act_args(cfg);
   a.params = params; a.x = x; a.dense = mult; a.out.q = q;
-  return launch_act<MODE_Q>(a, n_tiles(cfg), (hipStream_t)stream);
+  return launch_act<MODE_Q>(a, (hipStream_t)stream);
 }
 
 int swarm_act_step(const swarm_config* cfg, const float* params, float* state, const swarm_replay* replay,
                    const swarm_ctrl* ctrl, const swarm_act_out* out, void* stream) {
-  if (int e = check_cfg(cfg)) return e;
-  if (!ctrl || cfg->graph == SWARM_GRAPH_DENSE) return SWARM_E_BADARG;
-  ActArgs a = make_args(cfg);
+  if (int e = check_config(cfg, kCfgActGraph)) return e;
+  if (!ctrl) return SWARM_E_BADARG;
+  ActArgs a = make_act_args(cfg);
   a.params = params; a.state = state; a.ctrl = ctrl;
   if (replay) a.replay = *replay;
   if (out) a.out = *out;
-  return launch_act<MODE_TICK>(a, n_tiles(cfg), (hipStream_t)stream);
+  return launch_act<MODE_TICK>(a, (hipStream_t)stream);
 }
 
 int swarm_train_act_step(const swarm_config* cfg, const swarm_adam_cfg* hp, const swarm_learner* lr, float* state,
                          const swarm_replay* replay, const swarm_ctrl* ctrl, const swarm_act_out* out,
                          int32_t* sample_out, void* stream) {
-  if (int e = check_cfg(cfg)) return e;
-  if (!ctrl || !hp || !lr || cfg->graph == SWARM_GRAPH_DENSE || hp->world_size < 1 || hp->update_target_every < 1)
-    return SWARM_E_BADARG;
+  if (int e = check_config(cfg, kCfgActGraph)) return e;
+  if (!ctrl || !hp || !lr || hp->world_size < 1 || hp->update_target_every < 1) return SWARM_E_BADARG;
   if (cfg->net != SWARM_NET_GCN) return SWARM_E_UNSUPPORTED;   // GAT3: forward only
-  ActArgs a = make_args(cfg);
+  ActArgs a = make_act_args(cfg);
   a.state = state; a.ctrl = ctrl; a.learn = 1; a.lr = *lr; a.hp = *hp; a.sample_out = sample_out;
   a.grad_norm_out = const_cast<float*>(&ctrl->grad_norm);
   if (replay) a.replay = *replay;
   if (out) a.out = *out;
-  return launch_act<MODE_TICK>(a, n_tiles(cfg), (hipStream_t)stream);
+  return launch_act<MODE_TICK>(a, (hipStream_t)stream);
 }
 
 int swarm_rollout(const swarm_config* cfg, const float* params, float* state, int32_t n_ticks, uint32_t tick0,
                   float eps, const swarm_act_out* out, void* stream) {
-  if (int e = check_cfg(cfg)) return e;
-  if (n_ticks < 0 || cfg->graph == SWARM_GRAPH_DENSE) return SWARM_E_BADARG;
-  ActArgs a = make_args(cfg);
+  if (int e = check_config(cfg, kCfgActGraph)) return e;
+  if (n_ticks < 0) return SWARM_E_BADARG;
+  ActArgs a = make_act_args(cfg);
   a.params = params; a.state = state; a.n_ticks = n_ticks; a.tick0 = tick0; a.eps = eps;
   if (out) a.out = *out;
   if (n_ticks == 0) return 0;
-  return launch_act<MODE_ROLLOUT>(a, n_tiles(cfg), (hipStream_t)stream);
+  return launch_act<MODE_ROLLOUT>(a, (hipStream_t)stream);
 }
 
 #if SWARM_STAMPS

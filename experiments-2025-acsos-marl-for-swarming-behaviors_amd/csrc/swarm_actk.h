@@ -156,7 +156,7 @@ __device__ __forceinline__ void act_body(ActSmem<NS>& S, const int vb, const int
     const uint32_t filled = cc.filled_slots;
     const uint32_t ng = (filled + 1 < cap ? filled + 1 : cap) * (uint32_t)B;
     if (ng >= (uint32_t)A.hp.batch) {
-      const SampleKey sk = sample_key_cached(&cc, ng, A.k0 ^ ((uint32_t)A.env_offset * 0x9E3779B9u), A.k1, tick);
+      const SampleKey sk = sample_key_cached(&cc, ng, sample_salt_k0(A.k0, A.env_offset), A.k1, tick);
       ho_pub = sample_position(slot * (uint32_t)B + (uint32_t)d.gid, sk) < (uint32_t)A.hp.batch;
     }
   }
@@ -557,7 +557,7 @@ if (MODE == MODE_TICK && smp) {   // at the end of every wave: nothing waits on 
     const uint32_t filled = cc.filled_slots;
     const uint32_t ng = (filled + 1 < cap ? filled + 1 : cap) * (uint32_t)B;
     if (ng >= (uint32_t)A.hp.batch) {
-      const SampleKey sk = sample_key_cached(&cc, ng, A.k0 ^ ((uint32_t)A.env_offset * 0x9E3779B9u), A.k1, tick);
+      const SampleKey sk = sample_key_cached(&cc, ng, sample_salt_k0(A.k0, A.env_offset), A.k1, tick);
       const int nw = nvb * kActWPB;
       for (int i = vb * kActWPB + w + nw * d.lane; i < A.hp.batch; i += nw * 64)
         smp[i] = (int32_t)sample_index((uint32_t)i, sk);

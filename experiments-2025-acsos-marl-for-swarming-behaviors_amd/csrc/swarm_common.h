@@ -118,6 +118,13 @@ __host__ __device__ inline SampleKey sample_key(uint32_t n, uint32_t k0, uint32_
   s.n = n;
   return s;
 }
+// first key word of the replay-sampling stream: the seed's low word salted with the rank's
+// env_offset, so ranks draw different batches.  The acting blocks (which announce the rows a
+// tick samples), the TD blocks, the reduce's control block and swarm_sample_prepare all key
+// sample_key with this
+__host__ __device__ inline uint32_t sample_salt_k0(uint32_t k0, int env_offset) {
+  return k0 ^ ((uint32_t)env_offset * 0x9E3779B9u);
+}
 // the key of tick `rnd` from ctrl's cache when its tags match, else derived
 __device__ inline SampleKey sample_key_cached(const swarm_ctrl* c, uint32_t n, uint32_t k0, uint32_t k1, uint32_t rnd) {
   if (c->sample_tick == rnd && c->sample_n == n) {

@@ -6,7 +6,7 @@
 // GraphReplayBuffer.sample (:38-45), Adam(lr=1e-3) (:85), target sync (:131-133).
 #include <stdlib.h>
 
-#include "swarm_tdk.h"
+#include "swarm_launch.h"
 #include "swarm_peer.h"
 
 namespace swarm {
@@ -317,32 +317,14 @@ __global__ void ctrl_advance_kernel(swarm_ctrl* C, int capacity) {
 using namespace swarm;
 
 namespace {
-int td_slots(int N) { return N <= 8 ? 8 : (N <= 16 ? 16 : 32); }
-// one block per 32 node slots = 32 / NS sampled graphs
-int td_blocks(const swarm_config* cfg, int batch) {
-  const int gpb = kTdRows / td_slots(cfg->n_agents);
-  return (batch + gpb - 1) / gpb;
-}
-int td_max_blocks(const swarm_config* cfg, int batch) { return td_blocks(cfg, batch); }
-}  // namespace
-namespace {
-int check_td(const swarm_config* c, const swarm_adam_cfg* hp) {
-  if (!c || !hp || c->n_agents < 1 || c->n_agents > 32 || c->n_envs < 1 || hp->batch < 1) return SWARM_E_BADARG;
-  if (c->graph == SWARM_GRAPH_DENSE) return SWARM_E_BADARG;
-  if (c->graph < 0 || c->graph > 3) return SWARM_E_BADARG;
-  if (c->net != SWARM_NET_GCN) return SWARM_E_UNSUPPORTED;   // GAT3: forward only
-  if (c->graph == SWARM_GRAPH_KNN && (c->knn_k < 1 || c->knn_k > c->n_agents)) return SWARM_E_KNN_K;
-  if (c->graph == SWARM_GRAPH_RADIUS && !(c->radius > 0.0f)) return SWARM_E_BADARG;
-  if (hp->world_size < 1 || hp->update_target_every < 1) return SWARM_E_BADARG;
-  return 0;
-}
+int check_td(const swarm_config* c, const swarm_adam_cfg* hp) { return check_config(c, kCfgTd, hp); }
 }  // namespace
 
 extern "C" {
 
 int64_t swarm_td_workspace_floats(const swarm_config* cfg, int32_t batch) {
   if (!cfg || cfg->n_agents < 1 || cfg->n_agents > 32 || batch < 1) return SWARM_E_BADARG;
-  return (int64_t)(td_max_blocks(cfg, batch) * slab_floats_per_block());
+  return (int64_t)(td_blocks(cfg->n_agents, batch) * slab_floats_per_block());
 }
 
 int swarm_td_grad(const swarm_config* cfg, const swarm_adam_cfg* hp, const float* params, const float* target,
@@ -350,33 +332,15 @@ int swarm_td_grad(const swarm_config* cfg, const swarm_adam_cfg* hp, const float
                   float* slabs, void* stream) {
   if (int e = check_td(cfg, hp)) return e;
   if (!replay || !ctrl || !slabs || replay->capacity < 1) return SWARM_E_BADARG;
-  TdArgs a = {};
-  a.S = hp->batch; a.B = cfg->n_envs; a.N = cfg->n_agents; a.graph = cfg->graph; a.k = cfg->knn_k;
-  a.conv = cfg->conv; a.env_offset = cfg->env_offset;
-  a.k0 = (uint32_t)(cfg->seed & 0xFFFFFFFFu); a.k1 = (uint32_t)(cfg->seed >> 32);
-  a.radius = cfg->radius;
-  a.params = params; a.target = target; a.replay = *replay; a.ctrl = ctrl;
-  a.sample_in = sample_in; a.sample_out = sample_out; a.slabs = slabs;
-  a.gamma = hp->gamma;
-  a.grad_scale = (float)(2.0 / ((double)hp->batch * (double)cfg->n_agents));
-  const int nb = td_blocks(cfg, hp->batch);
-  a.n_slabs = nb;
-  hipStream_t st = (hipStream_t)stream;
-  const int spec = spec_of(a.graph, a.conv);   // training graphs are complete: GAT and GCN specialised
-#define SWARM_TD_LAUNCH1(NS, GS, NT, SP)                                                                       \
-  hipLaunchKernelGGL((td_kernel<NS, GS, SP>), dim3(nb), dim3(NT), 0, st, a.sample_in, a.replay.s, a.replay.s_next, \
-                     a.replay.r, a.replay.a, a.S, a.B, a.N, a.replay.capacity, a)
-#define SWARM_TD_LAUNCH(NS, GS, NT)                                                       \
-  do {                                                                                    \
-    if (spec == SPEC_COMPLETE_GAT) SWARM_TD_LAUNCH1(NS, GS, NT, SPEC_COMPLETE_GAT);      \
-    else if (spec == SPEC_COMPLETE_GCN) SWARM_TD_LAUNCH1(NS, GS, NT, SPEC_COMPLETE_GCN); \
-    else SWARM_TD_LAUNCH1(NS, GS, NT, SPEC_RUNTIME);                                      \
-  } while (0)
-  if (a.N <= 8) SWARM_TD_LAUNCH(16, 8, 128 * 2);
-  else if (a.N <= 16) SWARM_TD_LAUNCH(16, 16, 128 * 2);
-  else SWARM_TD_LAUNCH(32, 32, 128);
-#undef SWARM_TD_LAUNCH
-#undef SWARM_TD_LAUNCH1
+  const TdArgs a = make_td_args(cfg, hp, params, target, replay, ctrl, sample_in, sample_out, slabs);
+  with_slots<8, 16, 32>(a.N, [&](auto gs) {
+    constexpr int GS = decltype(gs)::value, NS = td_wave_slots(GS);
+    with_spec<TdSpecs>(a.graph, a.conv, [&](auto sp) {
+      hipLaunchKernelGGL((td_kernel<NS, GS, decltype(sp)::value>), dim3(a.n_slabs), dim3(128 * (kTdRows / NS)), 0,
+                         (hipStream_t)stream, a.sample_in, a.replay.s, a.replay.s_next, a.replay.r, a.replay.a, a.S, a.B,
+                         a.N, a.replay.capacity, a);
+    });
+  });
   return (int)hipGetLastError();
 }
 
@@ -388,7 +352,7 @@ int swarm_grad_reduce(const swarm_config* cfg, const swarm_adam_cfg* hp, const f
                       void* stream) {
   if (int e = check_td(cfg, hp)) return e;
   ReduceArgs a = {};
-  a.n_slabs = td_blocks(cfg, hp->batch); a.slabs = slabs; a.grad = grad;
+  a.n_slabs = td_blocks(cfg->n_agents, hp->batch); a.slabs = slabs; a.grad = grad;
   hipLaunchKernelGGL(grad_reduce_kernel<0>, dim3(kRedColBlocks), dim3(kRedCols * kRedGroups), 0,
                      (hipStream_t)stream, a.slabs, a.ctrl, a.n_slabs, a.advance, a);
   return (int)hipGetLastError();
@@ -400,15 +364,11 @@ static int reduce_advance(const swarm_config* cfg, const swarm_adam_cfg* hp, con
   if (!lr || !ctrl || replay_capacity < 1) return SWARM_E_BADARG;
   ReduceArgs a = {};
   if (peer) a.peer = *peer;
-  a.n_slabs = td_blocks(cfg, hp->batch); a.slabs = slabs; a.grad = lr->grad;
-#if SWARM_DIAG_FEWSLABS   // diagnostic builds only: the reduce reads K slabs (timing bound of a slab cut)
-  a.n_slabs = a.n_slabs < SWARM_DIAG_FEWSLABS ? a.n_slabs : SWARM_DIAG_FEWSLABS;
-#endif
+  a.n_slabs = diag_reduce_slabs(td_blocks(cfg->n_agents, hp->batch)); a.slabs = slabs; a.grad = lr->grad;
   a.advance = 1; a.lr = *lr; a.ctrl = ctrl;
   a.capacity = replay_capacity; a.B = cfg->n_envs; a.N = cfg->n_agents; a.batch = hp->batch;
   a.hp = *hp;
-  a.k0 = (uint32_t)(cfg->seed & 0xFFFFFFFFu) ^ ((uint32_t)cfg->env_offset * 0x9E3779B9u);
-  a.k1 = (uint32_t)(cfg->seed >> 32);
+  a.k0 = sample_salt_k0(seed_k0(cfg), cfg->env_offset); a.k1 = seed_k1(cfg);
   if (peer)
     hipLaunchKernelGGL(grad_reduce_kernel<1>, dim3(kRedColBlocks + 1 + kRedCopyBlocks), dim3(kRedCols * kRedGroups), 0,
                        (hipStream_t)stream, a.slabs, a.ctrl, a.n_slabs, a.advance, a);
@@ -456,9 +416,9 @@ int swarm_sample_prepare(const swarm_config* cfg, const swarm_adam_cfg* hp, int3
                          const swarm_ctrl* ctrl, int32_t* samples, void* stream) {
   if (int e = check_td(cfg, hp)) return e;
   if (!ctrl || !samples || replay_capacity < 1) return SWARM_E_BADARG;
-  const uint32_t k0 = (uint32_t)(cfg->seed & 0xFFFFFFFFu) ^ ((uint32_t)cfg->env_offset * 0x9E3779B9u);
   hipLaunchKernelGGL(sample_prepare_kernel, dim3((hp->batch + 255) / 256), dim3(256), 0, (hipStream_t)stream, ctrl,
-                     replay_capacity, cfg->n_envs, hp->batch, k0, (uint32_t)(cfg->seed >> 32), samples);
+                     replay_capacity, cfg->n_envs, hp->batch, sample_salt_k0(seed_k0(cfg), cfg->env_offset),
+                     seed_k1(cfg), samples);
   return (int)hipGetLastError();
 }
 

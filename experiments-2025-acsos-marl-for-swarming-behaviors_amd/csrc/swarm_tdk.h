@@ -17,6 +17,7 @@
 // slabs in a fixed order (bitwise run-to-run reproducible).
 #pragma once
 #include "swarm_adam.h"
+#include "swarm_diag.h"
 #include "swarm_dl.h"
 
 namespace swarm {
@@ -78,9 +79,6 @@ struct TdArgs {
 // as nt (td 8.4 vs 8.0 us) and as 4-B write-through sc1 (9.5 us; round 6 again: +0.1-0.2 us per
 // tick) they cost more; the dW1 / dW2 tiles' 16-B pieces are write-through (sst4)
 __device__ inline void slab_st(float* p, float v) { *p = v; }
-#ifndef SWARM_DIAG_FEWSLABS
-#define SWARM_DIAG_FEWSLABS 0   // diagnostic builds only: > 0 = only the first K TD blocks store slabs (timing bound)
-#endif
 
 // NS node slots per wave holding NS / GS graphs of GS slots (GS = 8 < NS = 16 packs two
 // N <= 8 graphs into one wave: every MFMA column is a real node, one wave per SIMD).
@@ -183,29 +181,17 @@ __device__ __forceinline__ void td_body(TdSmem<NS>& L, const int vb, const int32
   static_assert(kSlabCols == 16, "slab column blocks of 16");
   float* const slab_base = A.slabs + (size_t)vb * kSlabCols;
   const uint32_t slab_stride = (uint32_t)A.n_slabs * kSlabCols;
-#if SWARM_DIAG_FEWSLABS > 0
+  TD_DIAG_SLAB_STATE   // swarm_diag.h: nothing, and every block stores, in the product build
   auto sst_g = [&](int q, float v) {
-    if (vb < SWARM_DIAG_FEWSLABS) slab_st(slab_base + ((uint32_t)(q >> 4) * slab_stride + (uint32_t)(q & 15)), v);
+    if (TD_DIAG_STORES_SLAB(vb)) slab_st(slab_base + ((uint32_t)(q >> 4) * slab_stride + (uint32_t)(q & 15)), v);
   };
-#elif SWARM_DIAG_FEWSLABS < 0   // -1: blocks holding a graph of this tick's slot skip their stores; -2: the others do
-  bool diag_skip = false;   // set once the block knows whether it holds such a graph
-  auto sst_g = [&](int q, float v) {
-    if (!diag_skip) slab_st(slab_base + ((uint32_t)(q >> 4) * slab_stride + (uint32_t)(q & 15)), v);
-  };
-#else
-  auto sst_g = [&](int q, float v) { slab_st(slab_base + ((uint32_t)(q >> 4) * slab_stride + (uint32_t)(q & 15)), v); };
-#endif
 // the dW1 / dW2 tiles' 16-B pieces: four consecutive parameters q .. q + 3 (q % 4 == 0) of one
 // 16-column slab run, stored write-through (swarm_common.h st16_wt): the 1,312 of a slab's 1,674
 // floats leave the XCD's L2 as they are written instead of at the launch end (round 6: C2 -0.22,
 // C3 -0.43 us per tick, profiles/r06_ab_b2t_v3_*.jsonl; plain 16-B stores were neutral)
   static_assert(OFF_W1 % 16 == 0 && OFF_W2 % 16 == 0 && kHidden % 16 == 0, "16-B slab pieces");
   auto sst4 = [&](int q, f32x4 v) {
-#if SWARM_DIAG_FEWSLABS > 0
-    if (vb >= SWARM_DIAG_FEWSLABS) return;
-#elif SWARM_DIAG_FEWSLABS < 0
-    if (diag_skip) return;
-#endif
+    if (!TD_DIAG_STORES_SLAB(vb)) return;
     st16_wt(slab_base + ((uint32_t)(q >> 4) * slab_stride + (uint32_t)(q & 15)), v[0], v[1], v[2], v[3]);
   };
   auto sst = sst_g;
@@ -259,7 +245,7 @@ __device__ __forceinline__ void td_body(TdSmem<NS>& L, const int vb, const int32
   const uint32_t valid_slots = filled + 1 < cap ? filled + 1 : cap;
   const uint32_t n_graphs = valid_slots * (uint32_t)B;
   if (FUSED || !sample_in) {   // GraphReplayBuffer.sample: random.sample -> keyed permutation
-    const uint32_t k0 = A.k0 ^ ((uint32_t)A.env_offset * 0x9E3779B9u);
+    const uint32_t k0 = sample_salt_k0(A.k0, A.env_offset);
     const SampleKey sk = FUSED ? sample_key_cached(&cc, n_graphs, k0, A.k1, cc.tick)
                                : sample_key(n_graphs, k0, A.k1, A.ctrl->tick);
 #pragma unroll
@@ -347,12 +333,7 @@ __device__ __forceinline__ void td_body(TdSmem<NS>& L, const int vb, const int32
   bool pre = false;
 #pragma unroll
   for (int w2 = 0; w2 < GPB; ++w2) pre = pre || TB.insl[w2] != 0;
-#if SWARM_DIAG_PRE_ALL   // diagnostic builds only (tools/ab_build.py): every block on the pre path
-  pre = true;
-#endif
-#if SWARM_DIAG_FEWSLABS < 0
-  diag_skip = (SWARM_DIAG_FEWSLABS == -1) == pre;
-#endif
+  TD_DIAG_PRE(pre)
   pre = pre && online;
   const uint32_t tag = cc.tick + 1u;
   // granule address of this lane's node in a hand-off record: s at 0, s' at 4N, r at 8N, a at 9N

@@ -14,8 +14,7 @@
 // and have the lower block indices; the wait is bounded (kHoSpinLimit) and counted in the
 // workspace's error word, so the grid always drains.  Every other TD graph (slots written by
 // earlier ticks) runs concurrently with acting.
-#include "swarm_actk.h"
-#include "swarm_tdk.h"
+#include "swarm_launch.h"
 
 namespace swarm {
 
@@ -60,15 +59,7 @@ size_t rec_bytes(int B, int N) { return (size_t)B * ho_stride_granules(N) * 8; }
 
 extern "C" {
 
-int swarm_train_tick_supported(const swarm_config* cfg) {
-  if (!cfg || cfg->n_agents < 1 || cfg->n_agents > 16 || cfg->n_envs < 1 || cfg->net != SWARM_NET_GCN) return 0;
-  if (cfg->graph == SWARM_GRAPH_KNN && (cfg->knn_k < 1 || cfg->knn_k > cfg->n_agents)) return 0;
-  if (cfg->graph == SWARM_GRAPH_RADIUS && !(cfg->radius > 0.0f)) return 0;
-  return (cfg->graph == SWARM_GRAPH_COMPLETE || cfg->graph == SWARM_GRAPH_KNN || cfg->graph == SWARM_GRAPH_RADIUS) &&
-         (cfg->conv == SWARM_CONV_GAT || cfg->conv == SWARM_CONV_GCN) &&
-         (cfg->scenario == SWARM_GOTO || cfg->scenario == SWARM_OBSTACLE_AVOIDANCE ||
-          (cfg->scenario == SWARM_FLOCKING && cfg->n_agents >= 2));
-}
+int swarm_train_tick_supported(const swarm_config* cfg) { return check_config(cfg, kCfgTick) == 0; }
 
 int64_t swarm_train_tick_workspace_bytes(const swarm_config* cfg) {
   if (!swarm_train_tick_supported(cfg)) return SWARM_E_UNSUPPORTED;
@@ -87,60 +78,29 @@ int swarm_train_tick(const swarm_config* cfg, const swarm_adam_cfg* hp, const sw
   uint32_t* err = reinterpret_cast<uint32_t*>(ws);
   unsigned long long* rec = reinterpret_cast<unsigned long long*>(ws + err_bytes());
 
-  ActArgs a = {};
-  a.B = B; a.N = N; a.scenario = cfg->scenario; a.graph = cfg->graph; a.k = cfg->knn_k; a.conv = cfg->conv;
-  a.env_offset = cfg->env_offset; a.flags = cfg->flags;
-  a.k0 = (uint32_t)(cfg->seed & 0xFFFFFFFFu); a.k1 = (uint32_t)(cfg->seed >> 32); a.radius = cfg->radius;
+  ActArgs a = make_act_args(cfg);
   a.state = state; a.ctrl = ctrl; a.learn = 1; a.lr = *lr; a.hp = *hp; a.sample_out = nullptr;
   a.grad_norm_out = const_cast<float*>(&ctrl->grad_norm);
   a.replay = *replay;
   if (out) a.out = *out;
   a.ho_rec = rec;
 
-  TdArgs t = {};
-  t.S = hp->batch; t.B = B; t.N = N; t.graph = cfg->graph; t.k = cfg->knn_k; t.conv = cfg->conv;
-  t.env_offset = cfg->env_offset; t.k0 = a.k0; t.k1 = a.k1; t.radius = cfg->radius;
-  t.params = lr->w_nxt; t.target = lr->target; t.replay = *replay; t.ctrl = ctrl;
-  t.sample_in = nullptr; t.sample_out = sample_out; t.slabs = slabs;
-  t.gamma = hp->gamma;
-  t.grad_scale = (float)(2.0 / ((double)hp->batch * (double)N));
+  const TdArgs t = make_td_args(cfg, hp, lr->w_nxt, lr->target, replay, ctrl, nullptr, sample_out, slabs);
 
   TdFused x = {};
   x.lr = *lr; x.hp = *hp; x.ho_rec = rec; x.ho_err = err;
 
-  const int n_act = (B + kActWPB - 1) / kActWPB;
-  const int gs = N <= 8 ? 8 : 16;
-  const int n_td = (hp->batch + (kTdRows / gs) - 1) / (kTdRows / gs);
-  t.n_slabs = n_td;
-  const dim3 grid(n_act + n_td), block(256);
-  hipStream_t st = (hipStream_t)stream;
-  const float *g = lr->grad, *w = lr->w_cur, *m = lr->m_cur, *v = lr->v_cur;
-  const bool oa = cfg->scenario == SWARM_OBSTACLE_AVOIDANCE;
-  // complete graph (the reference's training graph) and GoTo's radius graph with GAT (the
-  // north_star graph, N <= 8): graph and conv fixed at compile time; others: the
-  // runtime-switched kernel
-  const int spec = spec_of(cfg->graph, cfg->conv);
-#define SWARM_TICK_LAUNCH(NSA, GS, SC, SP)                                                                      \
-  hipLaunchKernelGGL((tick_kernel<NSA, 16, GS, SC, SP>), grid, block, 0, st, ctrl, state, g, w, m, v, B, N, a, t, x)
-#define SWARM_TICK_LAUNCH2(NSA, GS, SC)                                               \
-  do {                                                                                 \
-    if (spec == SPEC_COMPLETE_GAT) SWARM_TICK_LAUNCH(NSA, GS, SC, SPEC_COMPLETE_GAT);  \
-    else if (spec == SPEC_COMPLETE_GCN) SWARM_TICK_LAUNCH(NSA, GS, SC, SPEC_COMPLETE_GCN); \
-    else SWARM_TICK_LAUNCH(NSA, GS, SC, SPEC_RUNTIME);                                 \
-  } while (0)
-  const bool fl = cfg->scenario == SWARM_FLOCKING;
-  if (N <= 8) {
-    if (fl) SWARM_TICK_LAUNCH2(8, 8, SWARM_FLOCKING);
-    else if (oa) SWARM_TICK_LAUNCH2(8, 8, SWARM_OBSTACLE_AVOIDANCE);
-    else if (spec == SPEC_RADIUS_GAT) SWARM_TICK_LAUNCH(8, 8, SWARM_GOTO, SPEC_RADIUS_GAT);
-    else SWARM_TICK_LAUNCH2(8, 8, SWARM_GOTO);
-  } else {
-    if (fl) SWARM_TICK_LAUNCH2(16, 16, SWARM_FLOCKING);
-    else if (oa) SWARM_TICK_LAUNCH2(16, 16, SWARM_OBSTACLE_AVOIDANCE);
-    else SWARM_TICK_LAUNCH2(16, 16, SWARM_GOTO);
-  }
-#undef SWARM_TICK_LAUNCH2
-#undef SWARM_TICK_LAUNCH
+  // acting blocks first, then one TD block per slab; which tick_kernel: TickSpecs (swarm_launch.h)
+  const dim3 grid((B + kActWPB - 1) / kActWPB + t.n_slabs), block(256);
+  with_slots<8, 16>(N, [&](auto ns) {
+    with_scenario(cfg->scenario, [&](auto sc) {
+      constexpr int NSA = decltype(ns)::value, SC = decltype(sc)::value;
+      with_spec<TickSpecs<NSA, SC>>(cfg->graph, cfg->conv, [&](auto sp) {
+        hipLaunchKernelGGL((tick_kernel<NSA, td_wave_slots(NSA), NSA, SC, decltype(sp)::value>), grid, block, 0,
+                           (hipStream_t)stream, ctrl, state, lr->grad, lr->w_cur, lr->m_cur, lr->v_cur, B, N, a, t, x);
+      });
+    });
+  });
   return (int)hipGetLastError();
 }
 

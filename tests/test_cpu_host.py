@@ -218,6 +218,200 @@ def test_fused_tick_support_and_workspace_host_side():
                                     None, None, None) == -4
 
 
+# ---- host error codes of every entry point, as literal tables (test_host_error_codes_are_pinned).
+# A named condition of a configuration c and a call variant v (v: which pointer is NULL, hp fields).
+_COND = {
+    "cfg NULL": lambda c, v: v.get("null") == "cfg",
+    "agents not 1..32": lambda c, v: c.N < 1 or c.N > 32,
+    "agents not 1..16": lambda c, v: c.N < 1 or c.N > 16,
+    "envs < 0": lambda c, v: c.B < 0,
+    "envs < 1": lambda c, v: c.B < 1,
+    "scenario": lambda c, v: c.scen not in (0, 1, 2),
+    "flocking alone": lambda c, v: c.scen == 2 and c.N < 2,
+    "forward net": lambda c, v: c.net != 0 and (c.net != 1 or c.conv != 0),
+    "net not GCN": lambda c, v: c.net != 0,
+    "graph not 0..3": lambda c, v: c.graph < 0 or c.graph > 3,
+    "dense": lambda c, v: c.graph == 2,
+    "dense, mult NULL": lambda c, v: c.graph == 2 and v.get("null") == "mult",
+    "conv": lambda c, v: c.conv not in (0, 1),
+    "knn k": lambda c, v: c.graph == 1 and (c.k < 1 or c.k > c.N),
+    "radius": lambda c, v: c.graph == 3 and not c.radius > 0,
+    "hp NULL": lambda c, v: v.get("null") == "hp",
+    "batch < 1": lambda c, v: v.get("batch", 8) < 1,
+    "world_size < 1": lambda c, v: v.get("ws", 1) < 1,
+    "update_target_every < 1": lambda c, v: v.get("ute", 200) < 1,
+    "capacity < 1": lambda c, v: v.get("cap", 4) < 1,
+    "n_ticks < 0": lambda c, v: v.get("n_ticks", 2) < 0,
+    "pointer NULL": lambda c, v: v.get("null") not in (None, "cfg", "hp", "mult"),
+    "replay.s NULL": lambda c, v: v.get("null_s", False),
+    "peer NULL": lambda c, v: v.get("null") == "peer",
+    "peer world_size": lambda c, v: v.get("null") != "hp" and v.get("ws", 1) != 1,
+}
+# Ordered (condition, code) rows: the first row that holds is what the call returns.
+_CFG = (("cfg NULL", -1), ("agents not 1..32", -1), ("envs < 0", -1), ("scenario", -1), ("flocking alone", -1),
+        ("forward net", -1), ("graph not 0..3", -1), ("conv", -1), ("knn k", -2), ("radius", -1))
+_TD = (("cfg NULL", -1), ("hp NULL", -1), ("agents not 1..32", -1), ("envs < 1", -1), ("batch < 1", -1), ("dense", -1),
+       ("graph not 0..3", -1), ("net not GCN", -4), ("knn k", -2), ("radius", -1), ("world_size < 1", -1),
+       ("update_target_every < 1", -1))
+_TICK = (("cfg NULL", -4), ("agents not 1..16", -4), ("envs < 1", -4), ("net not GCN", -4), ("knn k", -4), ("radius", -4),
+         ("graph not 0..3", -4), ("dense", -4), ("conv", -4), ("scenario", -4), ("flocking alone", -4))
+_TABLES = {
+    "swarm_state_floats": _CFG,
+    "swarm_td_workspace_floats": (("cfg NULL", -1), ("agents not 1..32", -1), ("batch < 1", -1)),
+    "swarm_train_tick_workspace_bytes": _TICK,
+    "swarm_env_reset": _CFG,
+    "swarm_env_sync_state": _CFG,
+    "swarm_env_step": _CFG + (("pointer NULL", -1),),
+    "swarm_build_graph": _CFG + (("dense", -1),),
+    "swarm_q_forward": _CFG + (("dense, mult NULL", -1),),
+    "swarm_act_step": _CFG + (("pointer NULL", -1), ("dense", -1)),
+    "swarm_train_act_step": _CFG + (("pointer NULL", -1), ("hp NULL", -1), ("dense", -1), ("world_size < 1", -1),
+                                    ("update_target_every < 1", -1), ("net not GCN", -4)),
+    "swarm_rollout": _CFG + (("n_ticks < 0", -1), ("dense", -1)),
+    "swarm_td_grad": _TD + (("pointer NULL", -1), ("capacity < 1", -1)),
+    "swarm_grad_reduce": _TD,
+    "swarm_reduce_advance": _TD + (("pointer NULL", -1), ("capacity < 1", -1)),
+    "swarm_reduce_advance_peer": (("peer NULL", -1), ("peer world_size", -1)) + _TD + (("pointer NULL", -1),
+                                                                                      ("capacity < 1", -1)),
+    "swarm_sample_prepare": _TD + (("pointer NULL", -1), ("capacity < 1", -1)),
+    "swarm_adam_step": _TD + (("pointer NULL", -1), ("capacity < 1", -1)),
+    "swarm_adam_flush": _TD + (("pointer NULL", -1),),
+    "swarm_train_tick": (("cfg NULL", -1), ("hp NULL", -1), ("pointer NULL", -1)) + _TICK + (
+        ("batch < 1", -1), ("world_size < 1", -1), ("update_target_every < 1", -1), ("capacity < 1", -1),
+        ("replay.s NULL", -1)),
+}
+# The call variants of each launching entry point besides the plain one: NULL pointers by argument
+# name, hp and other scalar violations.
+_HP_BAD = ({"batch": 0}, {"ws": 0}, {"ute": 0})
+_VARIANTS = {
+    "swarm_env_reset": (),
+    "swarm_env_sync_state": (),
+    "swarm_env_step": ({"null": "actions"},),
+    "swarm_build_graph": (),
+    "swarm_q_forward": ({"null": "mult"},),
+    "swarm_act_step": ({"null": "ctrl"},),
+    "swarm_train_act_step": ({"null": "ctrl"}, {"null": "hp"}, {"null": "lr"}) + _HP_BAD[1:],
+    "swarm_rollout": ({"n_ticks": -1},),
+    "swarm_td_grad": ({"null": "hp"}, {"null": "replay"}, {"null": "ctrl"}, {"null": "slabs"}, {"cap": 0}) + _HP_BAD,
+    "swarm_grad_reduce": ({"null": "hp"},) + _HP_BAD,
+    "swarm_reduce_advance": ({"null": "hp"}, {"null": "lr"}, {"null": "ctrl"}, {"cap": 0}) + _HP_BAD,
+    "swarm_reduce_advance_peer": ({"null": "peer"}, {"null": "hp"}, {"null": "lr"}, {"ws": 2}, {"cap": 0}) + _HP_BAD,
+    "swarm_sample_prepare": ({"null": "hp"}, {"null": "ctrl"}, {"null": "samples"}, {"cap": 0}) + _HP_BAD,
+    "swarm_adam_step": ({"null": "hp"}, {"null": "params"}, {"null": "target"}, {"null": "m"}, {"null": "v"},
+                        {"null": "grad"}, {"null": "ctrl"}, {"cap": 0}) + _HP_BAD,
+    "swarm_adam_flush": ({"null": "hp"}, {"null": "lr"}, {"null": "ctrl"}) + _HP_BAD,
+    "swarm_train_tick": ({"null": "hp"}, {"null": "lr"}, {"null": "state"}, {"null": "replay"}, {"null": "ctrl"},
+                         {"null": "slabs"}, {"null": "workspace"}, {"cap": 0}, {"null_s": True}) + _HP_BAD,
+}
+
+
+def test_host_error_codes_are_pinned():
+    """What every entry point returns before it would launch anything, over a grid of
+    configurations: the size queries on the whole grid, each launching entry point on the
+    configurations and call variants it rejects (1 stands in for every device pointer, so a call
+    the tables expect to pass is never made).  The tables above are a record of the library's
+    behaviour: the order of their rows is the order in which the checks fire."""
+    import collections
+    import itertools
+    L, lib = _host_lib()
+    C = collections.namedtuple("C", "N B scen graph k radius conv net")
+
+    def expect(fn, c, v, held=None):   # held: the conditions that hold for (c, {}), computed once per c
+        if held is not None and not v:
+            return next((code for name, code in _TABLES[fn] if name in held), 0)
+        return next((code for name, code in _TABLES[fn] if _COND[name](c, v)), 0)
+
+    structs = {}   # the argument structs of the variants, built once
+
+    class Args:   # the arguments of one call: cfg, and by need hp / lr / replay / peer / 1-or-NULL pointers
+        def __init__(self, cfg, v):
+            self.cfg, self.v, self.null, self.cap = cfg, v, v.get("null"), v.get("cap", 4)
+
+        def P(self, name):
+            return None if self.null == name else 1
+
+        def ref(self, name, key, make):
+            if self.null == name:
+                return None
+            if key not in structs:
+                structs[key] = make()
+            return ctypes.byref(structs[key])
+
+        def hp(self):
+            k = (self.v.get("batch", 8), self.v.get("ute", 200), self.v.get("ws", 1))
+            return self.ref("hp", k, lambda: L.SwarmAdamCfg(1e-3, 0.9, 0.999, 1e-8, 1.0, 0.99, *k, 0))
+
+        def lr(self):
+            return self.ref("lr", "lr", lambda: L.SwarmLearner(*([1] * 8)))
+
+        def rp(self):
+            s = None if self.v.get("null_s") else 1
+            return self.ref("replay", ("rp", self.cap, s), lambda: L.SwarmReplay(s, 1, 1, 1, self.cap, 0))
+
+        def peer(self):
+            return self.ref("peer", "peer", lambda: L.SwarmPeer(1, 0, (ctypes.c_void_p * L.PEER_MAX)(1), 1, 1, 0, 0))
+
+    args = {
+        "swarm_env_reset": lambda a: (a.cfg, 1, 0, None),
+        "swarm_env_sync_state": lambda a: (a.cfg, 1, 1, None),
+        "swarm_env_step": lambda a: (a.cfg, 1, a.P("actions"), None, None),
+        "swarm_build_graph": lambda a: (a.cfg, 1, 1, None),
+        "swarm_q_forward": lambda a: (a.cfg, 1, 1, a.P("mult"), 1, None),
+        "swarm_act_step": lambda a: (a.cfg, 1, 1, None, a.P("ctrl"), None, None),
+        "swarm_train_act_step": lambda a: (a.cfg, a.hp(), a.lr(), 1, None, a.P("ctrl"), None, None, None),
+        "swarm_rollout": lambda a: (a.cfg, 1, 1, a.v.get("n_ticks", 2), 0, 0.0, None, None),
+        "swarm_td_grad": lambda a: (a.cfg, a.hp(), 1, 1, a.rp(), a.P("ctrl"), None, None, a.P("slabs"), None),
+        "swarm_grad_reduce": lambda a: (a.cfg, a.hp(), 1, 1, None),
+        "swarm_reduce_advance": lambda a: (a.cfg, a.hp(), 1, a.lr(), a.cap, a.P("ctrl"), None),
+        "swarm_reduce_advance_peer": lambda a: (a.cfg, a.hp(), 1, a.lr(), a.cap, a.P("ctrl"), a.peer(), None),
+        "swarm_sample_prepare": lambda a: (a.cfg, a.hp(), a.cap, a.P("ctrl"), a.P("samples"), None),
+        "swarm_adam_step": lambda a: (a.cfg, a.hp(), a.P("params"), a.P("target"), a.P("m"), a.P("v"), a.P("grad"),
+                                      a.cap, a.P("ctrl"), None),
+        "swarm_adam_flush": lambda a: (a.cfg, a.hp(), a.lr(), a.P("ctrl"), None),
+        "swarm_train_tick": lambda a: (a.cfg, a.hp(), a.lr(), a.P("state"), a.rp(), a.P("ctrl"), None, a.P("slabs"),
+                                       a.P("workspace"), None, None),
+    }
+
+    def call(fn, c, v, cfg):
+        return getattr(lib, fn)(*args[fn](Args(None if v.get("null") == "cfg" else cfg, v)))
+
+    td_graphs_per_block = {8: 4, 16: 2, 32: 1}   # a TD block is 32 node slots; a graph takes 8, 16 or 32
+    grid = []
+    for N, B, scen, graph, radius, conv, net in itertools.product(
+            (0, 1, 2, 8, 16, 17, 32, 33), (-1, 0, 1), (0, 1, 2, 3), (0, 1, 2, 3, 4), (0.0, 0.3), (0, 1, 2),
+            (L.NET_GCN, L.NET_GAT3)):
+        grid += [C(N, B, scen, graph, k, radius, conv, net) for k in sorted({0, 1, N, N + 1})]
+    assert len(grid) > 20000
+    calls = collections.Counter()
+    for c in grid:
+        cfg = ctypes.byref(L.SwarmConfig(c.B, c.N, c.scen, c.graph, c.k, c.conv, 0, 0, 7, c.radius, c.net))
+        held = {name for name, holds in _COND.items() if holds(c, {})}
+        # ---- the size queries, on the whole grid
+        want = expect("swarm_state_floats", c, {}, held) or c.B * c.N * (5 if c.scen == 2 else 4)
+        assert lib.swarm_state_floats(cfg) == want, ("swarm_state_floats", c)
+        for batch in (0, 1, 8, 33):
+            slots = 8 if c.N <= 8 else 16 if c.N <= 16 else 32
+            want = expect("swarm_td_workspace_floats", c, {"batch": batch}) or \
+                -(-batch // td_graphs_per_block[slots]) * 1680
+            assert lib.swarm_td_workspace_floats(cfg, batch) == want, ("swarm_td_workspace_floats", c, batch)
+        code = expect("swarm_train_tick_workspace_bytes", c, {}, held)
+        assert lib.swarm_train_tick_supported(cfg) == (1 if code == 0 else 0), ("swarm_train_tick_supported", c)
+        assert lib.swarm_train_tick_workspace_bytes(cfg) == (code or 512 + c.B * (-(-10 * c.N // 16) * 16) * 8), c
+        # ---- the launching entry points, where they refuse.  The plain call on the whole grid,
+        #      the NULL-pointer / hp variants on one slice of it (every N class, one env)
+        for fn, variants in _VARIANTS.items():
+            for v in ({},) + (variants if c.B == 1 and c.N in (1, 8, 17, 33) else ()):
+                code = expect(fn, c, v, held)
+                if code != 0:
+                    assert call(fn, c, v, cfg) == code, (fn, c, v)
+                    calls[fn] += 1
+    assert lib.swarm_train_tick_supported(None) == 0 and lib.swarm_state_floats(None) == -1
+    assert lib.swarm_td_workspace_floats(None, 8) == -1 and lib.swarm_train_tick_workspace_bytes(None) == -4
+    for fn in _VARIANTS:
+        assert call(fn, grid[0], {"null": "cfg"}, None) == expect(fn, grid[0], {"null": "cfg"}) == -1, fn
+    assert all(calls[fn] > 1000 for fn in _VARIANTS), calls
+
+
 @pytest.mark.parametrize("n", [1, 5, 8, 12])
 def test_dense_forward_equals_edge_list_forward(golden_weights, n):
     params = O.unflatten_params(torch.tensor(golden_weights["go_to"][1]))
