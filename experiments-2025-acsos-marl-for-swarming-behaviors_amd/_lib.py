@@ -85,6 +85,8 @@ _PROTOS = {
     "swarm_build_graph": (c_int32, [POINTER(SwarmConfig), c_void_p, c_void_p, c_void_p]),
     "swarm_edges_to_mult": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "swarm_q_forward": (c_int32, [POINTER(SwarmConfig), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "swarm_q_backward": (c_int32, [POINTER(SwarmConfig), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p]),
     "swarm_act_step": (c_int32, [POINTER(SwarmConfig), c_void_p, c_void_p, POINTER(SwarmReplay), c_void_p,
                                  POINTER(SwarmActOut), c_void_p]),
     "swarm_train_act_step": (c_int32, [POINTER(SwarmConfig), POINTER(SwarmAdamCfg), POINTER(SwarmLearner), c_void_p,

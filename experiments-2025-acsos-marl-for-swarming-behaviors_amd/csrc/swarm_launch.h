@@ -22,6 +22,7 @@ constexpr CfgRules kCfgAct = {32, true, true, true, false, false};        // act
 constexpr CfgRules kCfgActGraph = {32, false, true, true, false, false};  // ... that build the graph themselves
 constexpr CfgRules kCfgTd = {32, false, false, false, true, true};        // TD, reduce, Adam entry points
 constexpr CfgRules kCfgTick = {16, false, false, true, true, false};      // swarm_train_tick
+constexpr CfgRules kCfgQBackward = {32, true, false, true, true, false};  // swarm_q_backward: kCfgAct for a learner
 // 0 or the first error, in the order the entry points have always reported them (tests/test_cpu_host.py)
 inline int check_config(const swarm_config* c, const CfgRules& r, const swarm_adam_cfg* hp = nullptr) {
   if (!c || c->n_agents < 1 || c->n_agents > r.max_agents || c->n_envs < (r.empty_ok ? 0 : 1)) return SWARM_E_BADARG;

@@ -8,6 +8,7 @@
 
 #include "swarm_launch.h"
 #include "swarm_peer.h"
+#include "swarm_qbk.h"
 
 namespace swarm {
 
@@ -353,6 +354,25 @@ int swarm_grad_reduce(const swarm_config* cfg, const swarm_adam_cfg* hp, const f
   if (int e = check_td(cfg, hp)) return e;
   ReduceArgs a = {};
   a.n_slabs = td_blocks(cfg->n_agents, hp->batch); a.slabs = slabs; a.grad = grad;
+  hipLaunchKernelGGL(grad_reduce_kernel<0>, dim3(kRedColBlocks), dim3(kRedCols * kRedGroups), 0,
+                     (hipStream_t)stream, a.slabs, a.ctrl, a.n_slabs, a.advance, a);
+  return (int)hipGetLastError();
+}
+
+// GCN.forward's backward for a caller's dL/dQ (swarm_qbk.h; kernels in swarm_qbk.hip), then the
+// slab sum of swarm_grad_reduce
+int swarm_q_backward(const swarm_config* cfg, const float* params, const float* x, const uint8_t* mult,
+                     const float* dq, float* workspace, float* grad, void* stream) {
+  if (int e = check_config(cfg, kCfgQBackward)) return e;
+  if (!params || !x || !dq || !workspace || !grad) return SWARM_E_BADARG;
+  if (cfg->graph == SWARM_GRAPH_DENSE && !mult) return SWARM_E_BADARG;
+  QbArgs q = {};
+  q.B = cfg->n_envs; q.N = cfg->n_agents; q.graph = cfg->graph; q.k = cfg->knn_k; q.conv = cfg->conv;
+  q.radius = cfg->radius; q.params = params; q.x = x; q.mult = mult; q.dq = dq; q.slabs = workspace;
+  q.n_slabs = td_blocks(q.N, q.B);
+  if (int e = qbk_launch(q, (hipStream_t)stream)) return e;
+  ReduceArgs a = {};
+  a.n_slabs = q.n_slabs; a.slabs = workspace; a.grad = grad;
   hipLaunchKernelGGL(grad_reduce_kernel<0>, dim3(kRedColBlocks), dim3(kRedCols * kRedGroups), 0,
                      (hipStream_t)stream, a.slabs, a.ctrl, a.n_slabs, a.advance, a);
   return (int)hipGetLastError();

@@ -6,8 +6,13 @@ with an identical ``state_dict`` layout, so ``data/models/*.pth`` load unchanged
 
 ``forward(data)`` runs GATConv(7->32, heads=1, add_self_loops=False) -> tanh ->
 lin1 -> relu -> lin2 for every graph of the batch in one HIP launch
-(``swarm_q_forward``).  It is an inference forward (no autograd graph): the
+(``swarm_q_forward``).  By default it is an inference forward (no autograd graph): the
 learner's backward is the fused hand-written one in ``swarm_td_grad``.
+``GCN(..., autograd=True)`` makes ``forward`` differentiable in the parameters: the same launch
+computes Q (bitwise the same values), and ``loss.backward()`` runs one ``swarm_q_backward`` call
+for whatever dL/dQ the loss produced, so the reference's ``train_step_dqn`` text (and any other
+loss) trains these kernels.  ``data.x`` gets no gradient: the reference never differentiates the
+observations.
 ``conv="gcn"`` selects the GCNConv variant (parity unpinned), which
 reuses conv1.lin.weight / conv1.bias and ignores the attention vectors.
 
@@ -25,7 +30,7 @@ import torch.nn as nn
 from . import _lib
 from ._lib import check, ptr, stream_ptr
 from .engine import param_order
-from .graph import Data, _lib_byref, _round4, edges_to_mult
+from .graph import Data, _lib_byref, _round4, edges_to_mult, q_backward
 
 
 class GATConvParams(nn.Module):
@@ -44,9 +49,34 @@ class GATConvParams(nn.Module):
         nn.init.uniform_(self.lin.weight, -bound, bound)
 
 
+class _QFunction(torch.autograd.Function):
+    """Q = GCN.forward(x) as one ``swarm_q_forward`` launch; backward = one ``swarm_q_backward``
+    call, its flat gradient sliced in ``param_order("gcn")``.  No gradient for x."""
+
+    @staticmethod
+    def forward(ctx, model, x, cfg, mult, *params):
+        ctx.flat = model.flat_params(x.device)   # the weights this Q was computed with
+        ctx.x, ctx.cfg, ctx.mult = x, cfg, mult
+        ctx.params = params
+        return model._q_forward(ctx.flat, x, cfg, mult)
+
+    @staticmethod
+    def backward(ctx, dq):
+        if ctx.cfg.n_envs == 0:   # an empty batch: zero gradients, nothing to launch
+            flat = torch.zeros(_lib.N_PARAMS, dtype=torch.float32, device=ctx.x.device)
+        else:
+            flat = q_backward(ctx.flat, ctx.x, ctx.cfg, ctx.mult, dq)
+        grads, o = [], 0
+        for i, ((_, shape), p) in enumerate(zip(param_order("gcn"), ctx.params)):
+            n = p.numel()
+            grads.append(flat[o:o + n].reshape(shape).to(p.device, p.dtype) if ctx.needs_input_grad[4 + i] else None)
+            o += n
+        return (None, None, None, None, *grads)
+
+
 class GCN(nn.Module):
     def __init__(self, input_dim: int = 7, hidden_dim: int = 32, output_dim: int = 9, conv: str = "gat",
-                 layers: int = 1):
+                 layers: int = 1, autograd: bool = False):
         super().__init__()
         shapes = {1: (7, 32, 9), 3: (7, 8, 9)}
         if shapes.get(layers) != (input_dim, hidden_dim, output_dim):
@@ -54,6 +84,9 @@ class GCN(nn.Module):
                              "Flocking checkpoints' GCN(7, 8, 9, layers=3)")
         if layers == 3 and conv != "gat":
             raise ValueError("the three-layer network is a GAT")
+        if layers == 3 and autograd:
+            raise ValueError("the three-layer network is forward only (no backward kernel): autograd=True needs "
+                             "GCN(7, 32, 9)")
         self.conv1 = GATConvParams(input_dim, hidden_dim)
         if layers == 3:
             self.conv2 = GATConvParams(hidden_dim, hidden_dim)
@@ -62,15 +95,17 @@ class GCN(nn.Module):
         self.lin2 = nn.Linear(hidden_dim, output_dim)
         self.conv = conv
         self.layers = layers
+        self.autograd = bool(autograd)
         self.net = "gat3" if layers == 3 else "gcn"
         self.net_id = _lib.NET_GAT3 if layers == 3 else _lib.NET_GCN
         self._flat = None
         self._flat_key = None
 
     @classmethod
-    def from_state_dict(cls, sd, conv: str = "gat") -> "GCN":
+    def from_state_dict(cls, sd, conv: str = "gat", autograd: bool = False) -> "GCN":
         """A model of the checkpoint's architecture (three GATConvs if it holds conv2), loaded."""
-        m = cls(7, 8, 9, conv, layers=3) if "conv2.lin.weight" in sd else cls(7, 32, 9, conv)
+        m = (cls(7, 8, 9, conv, layers=3, autograd=autograd) if "conv2.lin.weight" in sd
+             else cls(7, 32, 9, conv, autograd=autograd))
         m.load_state_dict(sd)
         return m
 
@@ -83,19 +118,22 @@ class GCN(nn.Module):
             self._flat_key = key
         return self._flat
 
+    def _q_forward(self, params, x, cfg, mult) -> torch.Tensor:
+        q = torch.empty(x.shape[0], 9, dtype=torch.float32, device=x.device)
+        check(_lib.load().swarm_q_forward(_lib_byref(cfg), ptr(params), ptr(x), ptr(mult), ptr(q), stream_ptr()),
+              "swarm_q_forward")
+        return q
+
     def forward(self, data: Data) -> torch.Tensor:
-        lib = _lib.load()
+        _lib.load()
         x = data.x.to("cuda", torch.float32).contiguous()
         conv = _lib.CONV_GAT if self.conv == "gat" else _lib.CONV_GCN
-        params = self.flat_params(x.device)
         M = x.shape[0]
-        q = torch.empty(M, 9, dtype=torch.float32, device=x.device)
         if data.swarm is not None:
             m = data.swarm
+            mult = None
             cfg = _lib.SwarmConfig(m["n_graphs"], m["n_nodes"], 0, m["graph"], m["k"], conv, 0, 0, 0,
                                    float(m.get("radius", 0.0)), self.net_id)
-            check(lib.swarm_q_forward(_lib_byref(cfg), ptr(params), ptr(x), None, ptr(q), stream_ptr()),
-                  "swarm_q_forward")
         else:
             G = data.num_graphs
             if M % G:
@@ -103,9 +141,12 @@ class GCN(nn.Module):
             N = M // G
             mult = edges_to_mult(data.edge_index, G, N)
             cfg = _lib.SwarmConfig(G, N, 0, _lib.GRAPH_DENSE, 0, conv, 0, 0, 0, 0.0, self.net_id)
-            check(lib.swarm_q_forward(_lib_byref(cfg), ptr(params), ptr(x), ptr(mult), ptr(q), stream_ptr()),
-                  "swarm_q_forward")
-        return q
+        if self.autograd and torch.is_grad_enabled():
+            sd = dict(self.named_parameters())
+            params = [sd[k] for k, _ in param_order(self.net)]
+            if any(p.requires_grad for p in params):
+                return _QFunction.apply(self, x.detach(), cfg, mult, *params)
+        return self._q_forward(self.flat_params(x.device), x, cfg, mult)
 
 
 __all__ = ["GCN", "GATConvParams", "_round4"]

@@ -147,6 +147,23 @@ def edges_to_mult(edge_index: torch.Tensor, n_graphs: int, n_nodes: int) -> torc
     return mult[: n_graphs * n_nodes * n_nodes].view(n_graphs, n_nodes, n_nodes)
 
 
+def q_backward(params: torch.Tensor, x: torch.Tensor, cfg: "_lib.SwarmConfig", mult: Optional[torch.Tensor],
+               dq: torch.Tensor) -> torch.Tensor:
+    """Gradient of ``(Q * dq).sum()`` with respect to the flat parameter vector (``swarm_q_backward``):
+    params [N_PARAMS], x [G*N, 7], dq [G*N, 9] on the GPU, ``cfg`` as passed to ``swarm_q_forward``
+    (``mult``: the dense multiplicities, or None).  Returns [N_PARAMS] float32 on the GPU."""
+    lib = _lib.load()
+    dq = dq.to(x.device, torch.float32).contiguous()
+    n_ws = lib.swarm_td_workspace_floats(_lib_byref(cfg), cfg.n_envs)
+    if n_ws < 0:
+        check(int(n_ws), "swarm_td_workspace_floats")
+    ws = torch.empty(n_ws, dtype=torch.float32, device=x.device)
+    grad = torch.empty(_lib.GRAD_FLOATS, dtype=torch.float32, device=x.device)
+    check(lib.swarm_q_backward(_lib_byref(cfg), ptr(params), ptr(x), ptr(mult), ptr(dq), ptr(ws), ptr(grad),
+                               stream_ptr()), "swarm_q_backward")
+    return grad[: _lib.N_PARAMS]
+
+
 def edge_index_from_mult(mult: torch.Tensor) -> torch.Tensor:
     """Inspection helper: dense multiplicity -> PyG edge_index (edges grouped by target)."""
     G, N, _ = mult.shape

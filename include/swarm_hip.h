@@ -218,6 +218,18 @@ int swarm_edges_to_mult(const int64_t* edge_index, int64_t n_edges, int32_t n_gr
 int swarm_q_forward(const swarm_config* cfg, const float* params, const float* x,
                     const uint8_t* mult, float* q, void* stream);
 
+/* Backward of GCN.forward (train_gcn_dqn.py:59-70) for a caller-supplied dL/dQ: the torch
+ * autograd of loss.backward() through model(batch) (train_gcn_dqn.py:122-124), parameters only.
+ * x [B*N][7], mult as swarm_q_forward; dq [B*N][9] = dL/dQ.
+ * grad[i] = sum over nodes n and actions a of dq[n][a] * dQ[n][a]/dtheta_i, flat PARAM_ORDER layout.
+ * grad holds SWARM_GRAD_FLOATS floats: [N_PARAMS] is written 0, and the clip norm's partials at
+ * SWARM_GRAD_SQ_BASE are written as by swarm_grad_reduce.
+ * workspace: swarm_td_workspace_floats(cfg, cfg->n_envs) floats, need not be zeroed.
+ * Two launches, no allocation, no host sync: capturable.
+ * Bitwise reproducible run to run.  n_envs >= 1; SWARM_NET_GCN only (else SWARM_E_UNSUPPORTED). */
+int swarm_q_backward(const swarm_config* cfg, const float* params, const float* x, const uint8_t* mult,
+                     const float* dq, float* workspace, float* grad, void* stream);
+
 /* Fused acting tick (train_gcn_dqn.py:161-172 / simulator.py:59-68):
  * graph -> GAT Q -> eps-greedy (ctrl->eps, Philox) -> env.step -> replay push
  * (replay may be NULL).  state updated in place. */

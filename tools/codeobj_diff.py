@@ -11,7 +11,8 @@ two objects are compared by names and bytes only (no instruction is inspected):
 A host-side refactor must leave all three equal: the kernels cannot tell who launched them.
 
 usage: python tools/codeobj_diff.py TREE_A TREE_B [--extra=-DSWARM_STAMPS=1 ...] [--keep DIR]
-Exit status 0 when every translation unit is identical, 1 otherwise.
+Translation units that only one tree has are named and left out of the comparison.
+Exit status 0 when every translation unit both trees have is identical, 1 otherwise.
 """
 import argparse
 import glob
@@ -93,14 +94,21 @@ def main():
     a = ap.parse_args()
     tmp = a.keep or tempfile.mkdtemp(prefix="codeobj_diff_")
     os.makedirs(tmp, exist_ok=True)
-    objs = {(t, s): os.path.join(tmp, f"{t}_{os.path.splitext(s)[0]}.o") for t in "ab" for s in B.SOURCES}
+    def has(tree, src):
+        return os.path.exists(os.path.join(glob.glob(os.path.join(tree, "*", "csrc"))[0], src))
+    # translation units both trees have are compared; one that only one tree has is new (or gone)
+    sources = [s for s in B.SOURCES if has(a.tree_a, s) and has(a.tree_b, s)]
+    for s in B.SOURCES:
+        if s not in sources:
+            print(f"{s}: only in tree {'A' if has(a.tree_a, s) else 'B'} (not compared)")
+    objs = {(t, s): os.path.join(tmp, f"{t}_{os.path.splitext(s)[0]}.o") for t in "ab" for s in sources}
     procs = [compile_start(a.tree_a if t == "a" else a.tree_b, s, a.extra, o) for (t, s), o in objs.items()]
     if any(p.wait() != 0 for p in procs):
         raise SystemExit("hipcc failed")
     print(f"codeobj_diff flags: {' '.join(B.FLAGS)} --cuda-device-only -Xoffload-linker --emit-relocs "
           f"{' '.join(a.extra)}".rstrip())
     same = True
-    for s in B.SOURCES:
+    for s in sources:
         da, db = describe(objs["a", s]), describe(objs["b", s])
         names = sorted(set(da) & set(db))
         code = [n for n in names if da[n][:2] != db[n][:2]]

@@ -1,0 +1,98 @@
+"""Time swarm_q_backward against the TD pair it shares its second launch with.
+
+Two chains of back-to-back launches on one stream, each between two HIP events (no host
+synchronisation inside a chain, so the launch-bound kernels overlap their launches as they do in a
+captured tick):
+  q_backward : swarm_q_backward                       (backward kernel + slab reduce)
+  td pair    : swarm_td_grad + swarm_grad_reduce      (TD kernel, in-kernel sampling + slab reduce)
+at S = B graphs of N agents, complete graph, GAT.  The chains alternate, `--repeats` times each, after
+a warm-up of both; the table gives the median and the spread of the per-call time of each chain.
+
+usage: python tools/qbwd_time.py [--calls 2000] [--repeats 7] [--out qbwd_time.json]
+Prints one JSON line per configuration.
+"""
+import argparse
+import ctypes
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import swarm_amd  # noqa: E402
+import swarm_amd._lib as L  # noqa: E402
+
+CONFIGS = (("GoTo", 8, 1024), ("ObstacleAvoidance", 12, 1024))
+
+
+def chain_us(fn, calls):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(calls):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) * 1e3 / calls
+
+
+def measure(scen, N, S, calls, repeats):
+    lib = L.load()
+    cap = 2
+    eng = swarm_amd.SwarmEngine(scen, N, S, seed=1, batch=S, replay_capacity=cap * S, update_target_every=1000,
+                                graph="complete", conv="gat")
+    g = torch.Generator().manual_seed(N)
+    eng.rep_s.copy_((torch.randn(cap, S, N, 4, generator=g) * 0.4).cuda())
+    eng.rep_s1.copy_((torch.randn(cap, S, N, 4, generator=g) * 0.4).cuda())
+    eng.rep_r.copy_(torch.randn(cap, S, N, generator=g).cuda())
+    eng.rep_a.copy_(torch.randint(0, 9, (cap, S, N), generator=g).to(torch.uint8).cuda())
+    eng.ctrl[2] = cap
+    eng.ctrl[1] = 0
+    s = eng.rep_s[0]
+    ids = torch.arange(N, dtype=torch.float32, device="cuda").view(1, N, 1).expand(S, N, 1)
+    goal = torch.tensor([-0.8, 0.8], device="cuda").expand(S, N, 2)
+    x = torch.cat([s, goal, ids], dim=-1).reshape(S * N, 7).contiguous()
+    dq = torch.randn(S * N, 9, generator=g).cuda()
+    cfg = L.SwarmConfig(S, N, eng.scenario_id, L.GRAPH_COMPLETE, 0, L.CONV_GAT, 0, 0, 0, 0.0, L.NET_GCN)
+    ws = torch.empty(lib.swarm_td_workspace_floats(ctypes.byref(cfg), S), dtype=torch.float32, device="cuda")
+    grad = torch.empty(L.GRAD_FLOATS, dtype=torch.float32, device="cuda")
+    st = L.stream_ptr()
+    args = (ctypes.byref(cfg), L.ptr(eng.params), L.ptr(x), None, L.ptr(dq), L.ptr(ws), L.ptr(grad), st)
+
+    def qb():
+        L.check(lib.swarm_q_backward(*args), "swarm_q_backward")
+
+    chains = {"q_backward": qb, "td_pair": eng.td_grad}
+    for fn in chains.values():   # warm-up: code objects loaded, clocks up
+        chain_us(fn, max(calls // 4, 10))
+    times = {k: [] for k in chains}
+    for _ in range(repeats):
+        for k, fn in chains.items():
+            times[k].append(chain_us(fn, calls))
+    out = {"scenario": scen, "n_agents": N, "graphs": S, "calls_per_chain": calls, "repeats": repeats,
+           "build": lib.swarm_build_info().decode()}
+    for k, v in times.items():
+        out[k + "_us"] = round(statistics.median(v), 3)
+        out[k + "_us_min_max"] = [round(min(v), 3), round(max(v), 3)]
+    out["ratio"] = round(out["q_backward_us"] / out["td_pair_us"], 3)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--calls", type=int, default=2000)
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    rows = [measure(scen, N, S, a.calls, a.repeats) for scen, N, S in CONFIGS]
+    for r in rows:
+        print(json.dumps(r))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(rows, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
