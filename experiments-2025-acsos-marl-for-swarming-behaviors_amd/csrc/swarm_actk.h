@@ -145,9 +145,17 @@ __device__ __forceinline__ void act_body(ActSmem<NS>& S, const int vb, const int
     slot = cc.write_slot;
   }
   const uint32_t genv = (uint32_t)(A.env_offset + d.gid);
+  // Training ticks of <= 8 slots (kDefer): the coin is first used after the argmax and the pair
+  // forces at the force sum, so neither is formed here, where they stood between the optimizer
+  // operands' arrival and the optimizer step: their straight-line part is issued in the empty
+  // VALU / SALU slots of the forward's lin1 / lin2 MFMA chains (dl_forward's hook, below), and
+  // what sits behind a branch (the contacts' forces, an exploring env's random actions) right
+  // after the forward.  The membership test and the s publication it gates stay here: the TD
+  // online wave starts its forward on s.
+  constexpr bool kDefer = MODE == MODE_TICK && NET == SWARM_NET_GCN && NS <= 8;
   // the first tick's eps-greedy coin only needs ctrl: drawn while the prologue's loads fly
-  const bool explore0 = (MODE != MODE_STEP && MODE != MODE_Q && eps > 0.0f) &&
-                        u01(philox4x32(tick, genv, STREAM_COIN, 0u, A.k0, A.k1).x) < eps;
+  bool explore0 = (!kDefer && MODE != MODE_STEP && MODE != MODE_Q && eps > 0.0f) &&
+                  u01(philox4x32(tick, genv, STREAM_COIN, 0u, A.k0, A.k1).x) < eps;
   // fused tick: is this env's transition in the TD batch drawn from this tick's slot?
   // (position of graph id slot * B + env in the keyed permutation < batch)
   bool ho_pub = false;
@@ -271,8 +279,33 @@ __device__ __forceinline__ void act_body(ActSmem<NS>& S, const int vb, const int
   // hoisted for graphs of <= 8 agents (one pair per lane); with 16 slots (4 pairs per lane) the
   // same hoist measured slower at C3 (18.17 -> 18.82 us per tick, 66 instead of 45 SGPR spills:
   // profiles/r05_ab_hoist_forces_c3.jsonl), so there the forces keep their place after the argmax
-  if (MODE != MODE_Q && kHoist) pair_forces();
-  // ...and the first tick's random actions of an exploring env (train_gcn_dqn.py:164-165)
+  // kDefer with one pair per lane (no list): the pair's distance and contact test are straight-line
+  // code and go into the forward's hook, every pair's slot zeroed there; the contacts' forces
+  // overwrite theirs after the forward.  The compacted form (a list, a loop) keeps its place here.
+  constexpr bool kDeferForces = kDefer && kHoist && !kCompact;
+  static_assert(!kDeferForces || (NS == 8 && SCEN != SWARM_OBSTACLE_AVOIDANCE), "one pair per lane, no obstacle pair");
+  float df_dx = 0.0f, df_dy = 0.0f, df_ds = 0.0f;
+  bool df_in = false;
+  const int df_of = (d.lane / NS) * kFbRow + 2 * (d.lane % NS);   // as cof[0] of pair_forces
+  auto pair_geometry0 = [&]() {   // sm.px / sm.py: the forward's (this tick's positions)
+    const int n = d.lane / NS, u = d.lane % NS;
+    const float pxn = sm.px[n], pyn = sm.py[n];
+    df_dx = pxn - sm.px[u];
+    df_dy = pyn - sm.py[u];
+    df_ds = norm2(df_dx, df_dy);
+    df_in = u < N && n < N && pair_contact(df_ds);
+    *reinterpret_cast<float2*>(fb + df_of) = make_float2(0.0f, 0.0f);
+  };
+  auto pair_contacts0 = [&]() {
+    if (df_in) {
+      float2 g;
+      contact_force(df_dx, df_dy, df_ds, g.x, g.y);
+      *reinterpret_cast<float2*>(fb + df_of) = g;
+    }
+  };
+  if (MODE != MODE_Q && kHoist && !kDeferForces) pair_forces();
+  // ...and the first tick's random actions of an exploring env (train_gcn_dqn.py:164-165; kDefer:
+  // no env explores yet, they are drawn after the forward)
   int ract0[CT];
 #pragma unroll
   for (int ct = 0; ct < CT; ++ct) {
@@ -284,6 +317,14 @@ __device__ __forceinline__ void act_body(ActSmem<NS>& S, const int vb, const int
       ract0[ct] = uniform_int(j == 0 ? wd.x : (j == 1 ? wd.y : (j == 2 ? wd.z : wd.w)), kActions);
     }
   }
+  // kDefer: the forward's hook (one training tick per launch: it == 0).  No branch in it, so that
+  // it shares a basic block with the MFMA chains; u01() >= 0, so eps <= 0 never explores
+  auto deferred0 = [&]() {
+    uint32_t coin = philox4x32(tick, genv, STREAM_COIN, 0u, A.k0, A.k1).x;
+    asm volatile("" : "+v"(coin));   // formed in the forward's block, not sunk to its first use
+    explore0 = u01(coin) < eps;
+    if constexpr (kDeferForces) pair_geometry0();
+  };
   if (MODE == MODE_TICK && NET == SWARM_NET_GCN && (kLearnCT || A.learn)) {
     // fused optimizer step of the previous tick's TD gradient (train_gcn_dqn.py:125-133)
     static_assert(64 * kActWPB == kAdamNT, "the act block is one Adam workgroup");
@@ -337,7 +378,20 @@ __device__ __forceinline__ void act_body(ActSmem<NS>& S, const int vb, const int
     if (MODE != MODE_STEP && NET == SWARM_NET_GAT3) {
       gat3_forward<NS>(P, d, N, graph, A.k, A.radius, A.dense, V, F);
     } else if (MODE != MODE_STEP) {
-      dl_forward<NS, 8>(P, d, N, graph, A.k, A.radius, conv, A.dense, V, false, F);
+      if constexpr (kDefer) dl_forward<NS, 8, NS>(P, d, N, graph, A.k, A.radius, conv, A.dense, V, false, F, deferred0);
+      else dl_forward<NS, 8>(P, d, N, graph, A.k, A.radius, conv, A.dense, V, false, F);
+    }
+    if constexpr (kDefer) {   // the deferred work's branches: pairs in contact, an exploring env
+      if constexpr (kDeferForces) pair_contacts0();
+      if (explore0) {
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct) {
+          const int agent = min(16 * ct + c, N - 1);
+          const u32x4 wd = philox4x32(tick, genv, STREAM_RAND_ACTION, (uint32_t)(agent >> 2), A.k0, A.k1);
+          const int j = agent & 3;
+          ract0[ct] = uniform_int(j == 0 ? wd.x : (j == 1 ? wd.y : (j == 2 ? wd.z : wd.w)), kActions);
+        }
+      }
     }
     if (it == 0) SWARM_STAMP(2);
 

@@ -397,9 +397,17 @@ __device__ inline void knn_masks_wave(int lane, int N, int k, WSmall<NS>& sm, fl
 // Full GCN.forward.  F.x must hold the lane's features (zero for nodes >= N).  P is the
 // padded LDS weight image.  Writes the H rows (and T / R rows if keep_tr) of V, the
 // per-node scalars of V.sm, and leaves F.t / F.zr / F.cf / F.q for the backward.
-template <int NS, int SB = -1, int GS = NS>
+// HOOK: work of the caller that needs no result of the forward, called once between lin1's
+// operand reads and its first MFMA: straight-line code there is issued in the VALU / SALU slots
+// under the lin1 and lin2 MFMA chains (24 MFMAs that wait on each other and leave those slots
+// empty).  sm.px / sm.py are complete when it runs.  Empty by default: no code.
+struct DlNoHook {
+  __device__ __forceinline__ void operator()() const {}
+};
+template <int NS, int SB = -1, int GS = NS, class HOOK = DlNoHook>
 __device__ inline void dl_forward(const float* __restrict__ P, const DGeom<NS>& d, int N, int graph, int k, float radius, int conv,
-                                  const uint8_t* __restrict__ dense, const WView<NS>& V, bool keep_tr, DFwd<NS>& F) {
+                                  const uint8_t* __restrict__ dense, const WView<NS>& V, bool keep_tr, DFwd<NS>& F,
+                                  const HOOK& hook = HOOK()) {
 #define DF_STAMP(i) do { if (SB >= 0) SWARM_STAMP(SB + (i)); } while (0)
   constexpr int CT = DGeom<NS>::CT;
   WSmall<NS>& sm = *V.sm;
@@ -591,6 +599,7 @@ __device__ inline void dl_forward(const float* __restrict__ P, const DGeom<NS>& 
     const float4 bb0 = *reinterpret_cast<const float4*>(P + L_B1 + 4 * p);
     const float4 bb1 = *reinterpret_cast<const float4*>(P + L_B1 + 16 + 4 * p);
     const float b1v[2][4] = {{bb0.x, bb0.y, bb0.z, bb0.w}, {bb1.x, bb1.y, bb1.z, bb1.w}};
+    hook();
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) {
       // the two output tiles' chains interleaved (independent accumulators: 32-cycle issue
