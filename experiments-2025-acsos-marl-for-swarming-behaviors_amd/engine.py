@@ -247,8 +247,10 @@ class SwarmEngine:
                                           stream_ptr()), "swarm_ctrl_advance")
 
     def rollout(self, n_ticks: int, tick0: int = 0, eps: float = 0.0, traj: bool = False, params=None):
-        """Acting-only rollout in one launch.  Returns per-env sums (and per-tick
-        trajectories when traj=True)."""
+        """Acting-only rollout in one launch; tick t is keyed tick0 + t.  Returns ``reward`` [B, N],
+        each agent's sum over the ticks; ``hits`` [B], the env's sum over the ticks; ``avg_dist``
+        [B], the last tick's mean goal distance (not a sum); ``obs`` [B, N, 6], the final
+        observation; and with traj=True every tick's ``traj_pos``, ``traj_dist``, ``traj_hits``."""
         dev = self.device
         res = dict(reward=torch.zeros(self.B, self.N, device=dev), hits=torch.zeros(self.B, device=dev),
                    avg_dist=torch.zeros(self.B, device=dev), obs=torch.zeros(self.B, self.N, 6, device=dev))

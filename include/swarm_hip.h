@@ -334,7 +334,13 @@ int swarm_adam_flush(const swarm_config* cfg, const swarm_adam_cfg* hp, const sw
 
 /* Acting-only rollout of n_ticks ticks with frozen weights in ONE launch
  * (Simulator.run_simulation, simulator.py:59-93, greedy when eps = 0).
- * out->reward / avg_dist / hits accumulate per-env sums over the ticks. */
+ * Tick t draws its coin and random actions with the key tick0 + t.  Of out (any pointer may be
+ * null): reward [B][N] is each agent's sum over the ticks (fp32, in tick order); hits [B] is the
+ * env's sum over the ticks; avg_dist [B] is the LAST tick's mean goal distance (Simulator's
+ * "Distance (end)"), not a sum; obs [B][N][6] is the final observation (the state after the last
+ * tick, then the goal); traj_pos / traj_dist / traj_hits hold every tick's positions, mean goal
+ * distance and hits.  n_ticks = 0 returns 0 and writes nothing.
+ * (tests/test_gpu_rollout_matrix.py) */
 int swarm_rollout(const swarm_config* cfg, const float* params, float* state,
                   int32_t n_ticks, uint32_t tick0, float eps, const swarm_act_out* out, void* stream);
 
