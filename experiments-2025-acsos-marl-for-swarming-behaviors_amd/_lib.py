@@ -59,6 +59,14 @@ class SwarmLearner(ctypes.Structure):
     _fields_ = [(n, c_void_p) for n in ("w_cur", "w_nxt", "m_cur", "m_nxt", "v_cur", "v_nxt", "target", "grad")]
 
 
+class SwarmPopMember(ctypes.Structure):
+    """One member of a population (swarm_pop_member): what swarm_train_tick and swarm_reduce_advance
+    take for a lone learner.  The array of them lives in device memory (population.py)."""
+    _fields_ = [("seed", c_uint64), ("state", c_void_p), ("replay", SwarmReplay), ("lr", SwarmLearner),
+                ("ctrl", c_void_p), ("out", SwarmActOut), ("slabs", c_void_p), ("workspace", c_void_p),
+                ("sample_out", c_void_p)]
+
+
 PEER_MAX = 8
 PEER_HANDLE_BYTES = 64
 PEER_SEQ_WORDS = 256
@@ -113,6 +121,9 @@ _PROTOS = {
     "swarm_train_tick": (c_int32, [POINTER(SwarmConfig), POINTER(SwarmAdamCfg), POINTER(SwarmLearner), c_void_p,
                                    POINTER(SwarmReplay), c_void_p, POINTER(SwarmActOut), c_void_p, c_void_p,
                                    c_void_p, c_void_p]),
+    "swarm_pop_train_tick": (c_int32, [POINTER(SwarmConfig), POINTER(SwarmAdamCfg), c_void_p, c_int32, c_void_p]),
+    "swarm_pop_reduce_advance": (c_int32, [POINTER(SwarmConfig), POINTER(SwarmAdamCfg), c_void_p, c_int32,
+                                           c_void_p]),
     "swarm_peer_buffer_bytes": (c_int64, []),
     "swarm_peer_alloc": (c_int32, [POINTER(c_void_p)]),
     "swarm_peer_free": (c_int32, [c_void_p]),

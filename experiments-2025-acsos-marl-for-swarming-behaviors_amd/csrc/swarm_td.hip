@@ -9,6 +9,7 @@
 #include "swarm_launch.h"
 #include "swarm_peer.h"
 #include "swarm_qbk.h"
+#include "swarm_reduce.h"
 
 namespace swarm {
 
@@ -24,208 +25,13 @@ __global__ __launch_bounds__(128 * (kTdRows / NS)) void td_kernel(const int32_t*
   td_body<NS, GS, SPEC>(L, blockIdx.x, sample_in, rs, rs_next, rr, ra, S, B, N, capacity, A, TdFused{});
 }
 
-// ---------------------------------------------------------------- slab reduction
-// block = 256 threads covers 64 columns; thread (col, part) sums a contiguous quarter
-// of the slabs, quarters combined in order: fixed order -> bitwise reproducible.
-struct ReduceArgs {
-  int n_slabs;
-  const float* slabs;
-  float* grad;
-  int advance;            // fused tick: copy *_nxt -> *_cur and advance ctrl
-  swarm_learner lr;
-  swarm_ctrl* ctrl;
-  int capacity, B, N, batch;
-  swarm_adam_cfg hp;
-  uint32_t k0, k1;        // replay-sampling key (seed ^ rank salt)
-  swarm_peer peer;        // PEER = 1: the all-reduce over the ranks' exchange buffers (swarm_peer.h)
-};
-
-// 1024 threads = 16 columns x 64 slab groups (105 column blocks: the 1.7 MB of freshly
-// written slabs is read by many CUs at once, 16 KB each); group g sums a contiguous run of
-// slabs with every load issued before the ordered adds, then the 64 group sums of a column
-// are added in a fixed two-level order (8 runs of 8, then the 8 run sums): bitwise
-// reproducible run to run.  Advance mode adds one control block (the last): it prepares
-// and stores the whole ctrl update (Adam scalars of the next step in double, the next
-// tick's sampling key) in parallel with the column blocks, so no column block waits on it.
-// Three more blocks copy w / m / v _nxt -> _cur (one array each), beside the column blocks.
-#ifndef SWARM_RED_GROUPS
-#define SWARM_RED_GROUPS 64   // test builds: 16 (256-thread blocks, so 8 ranks' peer reduces fit one GPU)
-#endif
-constexpr int kRedCols = 16;      // columns per reduce block
-constexpr int kRedGroups = SWARM_RED_GROUPS;   // slab groups per column (consecutive slabs each)
-constexpr int kRedRuns = kRedGroups / 8;
-constexpr int kRedChunk = 8;      // slabs per load chunk of a group
-constexpr int kRedColBlocks = (N_PARAMS + 1 + kRedCols - 1) / kRedCols;
-constexpr int kRedCopyBlocks = 3;
-
-// ---- the ctrl advance of one tick (the reduce launch's control block).  Every thread of the
-//      block calls it; thread 0 advances the counters and the Adam scalars, thread 64 derives the
-//      next tick's sampling key; both read ctrl before the barrier and write after it.
-struct RedCtrl {
-  int capacity, B, batch;
-  swarm_adam_cfg hp;
-  uint32_t k0, k1;   // replay-sampling key (seed ^ rank salt)
-};
-
-__device__ inline void red_control(swarm_ctrl* C, const RedCtrl& A) {
-  const int t = threadIdx.x;
-  uint32_t c_trained = 0, c_step = 0, c_tick = 0, c_slot = 0, c_filled = 0;
-  double b1p = 1.0, b2p = 1.0;
-  float next_step_size = 0.0f, next_inv_bc2 = 0.0f;
-  SampleKey nk = {};
-  uint32_t nk_n = 0, nk_tick = 0;
-  const uint32_t cap = (uint32_t)A.capacity;
-  if (t == 0) {
-    // a held rank (peer_hold: an expired exchange wait) applied no step this tick
-    c_trained = C->peer_hold ? 0u : C->trained;
-    c_step = C->adam_step; c_tick = C->tick; c_slot = C->write_slot; c_filled = C->filled_slots;
-    b1p = ctrl_get_double(C, CTRL_B1POW);
-    b2p = ctrl_get_double(C, CTRL_B2POW);
-    if (c_trained) {   // the step this tick's act kernel applied
-      b1p = b1p * adam_beta1(A.hp);
-      b2p = b2p * adam_beta2(A.hp);
-      adam_next_scalars(A.hp, b1p, b2p, next_step_size, next_inv_bc2);
-    }
-  } else if (t == 64) {
-    const uint32_t filled = C->filled_slots;
-    const uint32_t f1 = filled + 1 < cap ? filled + 1 : cap;   // filled after this tick
-    nk_n = (f1 + 1 < cap ? f1 + 1 : cap) * (uint32_t)A.B;       // graphs the next tick samples from
-    nk_tick = C->tick + 1;
-    nk = sample_key(nk_n, A.k0, A.k1, nk_tick);
-  }
-  __syncthreads();
-  if (t == 0) {   // record the pending update, advance the tick
-    const uint32_t valid_slots = c_filled + 1 < cap ? c_filled + 1 : cap;
-    const uint32_t trained = valid_slots * (uint32_t)A.B >= (uint32_t)A.batch ? 1u : 0u;
-    if (c_trained) {
-      C->adam_step = c_step + 1;
-      ctrl_set_double(C, CTRL_B1POW, b1p);
-      ctrl_set_double(C, CTRL_B2POW, b2p);
-      C->adam_step_size = next_step_size;
-      C->adam_inv_bc2 = next_inv_bc2;
-    }
-    C->trained = trained;
-    // (float)(1 - beta) of the Adam step, rewritten every tick from the launch's double
-    // hyper-parameters: a control block that skipped swarm_ctrl_init (zero-filled) has its
-    // first optimizer step pending only after this write, so no step runs with 0 here
-    C->one_m_beta1 = (float)(1.0 - adam_beta1(A.hp));
-    C->one_m_beta2 = (float)(1.0 - adam_beta2(A.hp));
-    C->tick = c_tick + 1;
-    C->write_slot = (c_slot + 1) % cap;
-    C->filled_slots = valid_slots;
-  } else if (t == 64) {
-    C->sample_key[0] = nk.rk[0]; C->sample_key[1] = nk.rk[1]; C->sample_key[2] = nk.rk[2]; C->sample_key[3] = nk.rk[3];
-    C->sample_bits = (uint32_t)nk.bits;
-    C->sample_n = nk_n;
-    C->sample_tick = nk_tick;
-  }
-}
-
-static_assert(kRedGroups % 8 == 0 && kRedCols * kRedGroups <= 1024, "reduce geometry");
-static_assert(kRedColBlocks <= kPeerSeqRegion, "peer seq region");
-static_assert(kRedColBlocks == kGradSqCount && kRedCols == 16, "one norm partial per column block");
+// ---------------------------------------------------------------- slab reduction (swarm_reduce.h;
+// the block's statements: swarm_reduce_body.h, shared with swarm_pop.hip)
 // slabs / ctrl / geometry preloaded into SGPRs (kernarg preload): the slab loads issue at wave start.
-// PEER = 1 (swarm_reduce_advance_peer): each column block then exchanges its 16 column sums with
-// the other ranks (swarm_peer.h) and writes grad = their rank-ordered sum: the all-reduce costs
-// one xGMI store + poll inside this launch instead of a collective launch after it.
 template <int PEER>
 __global__ __launch_bounds__(kRedCols * kRedGroups) void grad_reduce_kernel(const float* slabs, swarm_ctrl* ctrl,
                                                                             int n_slabs, int advance, ReduceArgs A) {
-  __shared__ float part[kRedGroups][kRedCols];
-  __shared__ float part2[kRedRuns][kRedCols];
-  __shared__ float peer_rv[PEER ? SWARM_PEER_MAX : 1][kRedCols];
-  __shared__ float sqv[kRedCols];
-  SWARM_RTSTAMP(22);
-  SWARM_STAMP(28);
-  swarm_ctrl* C = ctrl;
-  if ((int)blockIdx.x > kRedColBlocks) {   // advance mode: a copy-back block
-    const int j = (int)blockIdx.x - kRedColBlocks - 1;
-    const float4* src = reinterpret_cast<const float4*>(j == 0 ? A.lr.w_nxt : (j == 1 ? A.lr.m_nxt : A.lr.v_nxt));
-    float4* dst = reinterpret_cast<float4*>(j == 0 ? A.lr.w_cur : (j == 1 ? A.lr.m_cur : A.lr.v_cur));
-    if ((int)threadIdx.x < N_PARAMS_PAD / 4) dst[threadIdx.x] = src[threadIdx.x];
-    return;
-  }
-  if ((int)blockIdx.x == kRedColBlocks) {   // advance mode: the control block (red_control)
-    RedCtrl rc;
-    rc.capacity = A.capacity; rc.B = A.B; rc.batch = A.batch; rc.hp = A.hp; rc.k0 = A.k0; rc.k1 = A.k1;
-    red_control(C, rc);
-    return;
-  }
-  const int c = threadIdx.x % kRedCols;
-  const int col = blockIdx.x * kRedCols + c;
-  const int q = threadIdx.x / kRedCols;
-  const int per = (n_slabs + kRedGroups - 1) / kRedGroups;
-  const int b0 = q * per, b1 = min(n_slabs, b0 + per);
-  // first chunk of this thread's slab column in flight before anything else.  Column col of
-  // slab b is scol[16 b] (swarm_common.h slab_index): one 64-bit base per thread, 32-bit offsets
-  constexpr int kChunk = kRedChunk;
-  static_assert(kSlabCols == 16, "slab column blocks of 16");
-  const float* const scol = slabs + ((size_t)(col >> 4) * (size_t)n_slabs * kSlabCols + (size_t)(col & 15));
-  float v0[kChunk];
-#pragma unroll
-  for (int j = 0; j < kChunk; ++j)
-    v0[j] = (col <= N_PARAMS && b0 + j < b1) ? scol[(uint32_t)(b0 + j) * kSlabCols] : 0.0f;
-  float s = v0[0];
-#pragma unroll
-  for (int j = 1; j < kChunk; ++j) s = s + v0[j];
-  if (col <= N_PARAMS) {
-    for (int b = b0 + kChunk; b < b1; b += kChunk) {
-      float v[kChunk];
-#pragma unroll
-      for (int j = 0; j < kChunk; ++j) v[j] = (b + j < b1) ? scol[(uint32_t)(b + j) * kSlabCols] : 0.0f;
-#pragma unroll
-      for (int j = 0; j < kChunk; ++j) s = s + v[j];
-    }
-  }
-  SWARM_STAMP(29);
-  part[q][c] = s;
-  __syncthreads();
-  SWARM_STAMP(30);
-  if (q < kRedRuns) {
-    float r = part[8 * q][c];
-#pragma unroll
-    for (int gi = 1; gi < 8; ++gi) r = r + part[8 * q + gi][c];
-    part2[q][c] = r;
-  }
-  __syncthreads();
-  float gcol = 0.0f;   // q == 0: this column's gradient as written to grad
-  if (q == 0 && col <= N_PARAMS) {
-    float tot = part2[0][c];
-#pragma unroll
-    for (int gi = 1; gi < kRedRuns; ++gi) tot = tot + part2[gi][c];
-    if (PEER) part[0][c] = tot;   // part[0] is free again: this rank's column sums
-    else A.grad[col] = tot;
-    gcol = tot;
-    // this rank's loss of the update (0 when skipped: the TD launch wrote zero slabs)
-    if (advance && col == N_PARAMS) C->loss = tot / (float)((size_t)A.batch * A.N);
-  }
-  if (PEER) {
-    __syncthreads();
-    peer_exchange<kRedCols>(A.peer, 0, blockIdx.x, q, c, col, N_PARAMS + 1, part[0], peer_rv, &C->peer_hold);
-    if (q == 0 && col <= N_PARAMS) {
-      float tot = peer_rv[0][c];
-      for (int w = 1; w < A.peer.world_size; ++w) tot = tot + peer_rv[w][c];
-      A.grad[col] = tot;
-      gcol = tot;
-    }
-  }
-  // the clip norm's partial of these 16 columns = parameter group blockIdx.x (swarm_adam.h):
-  // lanes 0-15 of wave 0 hold the columns; squares as the optimizer step forms them (scaled by
-  // 1/W first when W > 1), the float4 sums ((a + b) + c) + d by lanes 0-3, then their quad sum
-  if (q == 0) {
-    float g = col < N_PARAMS ? gcol : 0.0f;
-    if (A.hp.world_size > 1) g = g * (1.0f / (float)A.hp.world_size);
-    sqv[c] = g * g;
-  }
-  wave_lds_sync();   // sqv is written and read by wave 0 only
-  if (threadIdx.x < 4) {
-    const int f = threadIdx.x;
-    const float d = ((sqv[4 * f] + sqv[4 * f + 1]) + sqv[4 * f + 2]) + sqv[4 * f + 3];
-    const float sq = quad_sum(d);
-    if (f == 0) A.grad[kGradSqBase + blockIdx.x] = sq;
-  }
-  SWARM_STAMP(31);
-  SWARM_RTSTAMP(23);
+#include "swarm_reduce_body.h"
 }
 
 // ---------------------------------------------------------------- clip + Adam + target sync

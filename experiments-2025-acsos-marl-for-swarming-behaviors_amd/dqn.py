@@ -28,6 +28,7 @@ from . import _lib
 from .engine import SwarmEngine, flatten_state_dict, glorot_init, unflatten_params
 from .gcn import GCN
 from .graph import Batch, Data, create_graph_from_observations
+from .population import SwarmPopulation
 
 
 class SummaryWriter:
@@ -235,6 +236,101 @@ class DQNTrainer:
             for i in range(len(self.episode_losses)):
                 if (i + 1) % 10 == 0:   # reference quirk: losses indexed with i // 10 (:231)
                     w.writerow([i, float(self.episode_rewards[i // 10]), self.episode_losses[i // 10]])
+
+
+class PopulationTrainer:
+    """Several ``DQNTrainer`` objects over one scenario and agent count (the reference's seeds
+    0-9 of one experiment, train_gcn_dqn.py:262-290) trained together: their engines become the
+    members of one ``SwarmPopulation``, so a training tick of all of them is two launches.
+
+    ``train_model(config)`` runs the loop of ``DQNTrainer.train_model`` for all trainers at once and
+    leaves each trainer as its own ``train_model`` would: the same episode lists and writer scalars,
+    the same ``.pth`` and ``.csv`` files (members compute a lone engine's bits)."""
+
+    def __init__(self, trainers):
+        self.trainers = list(trainers)
+        first = self.trainers[0]
+        for t in self.trainers:
+            if (t.env.max_steps, t.env.n_agents, t.use_graph) != (first.env.max_steps, first.env.n_agents,
+                                                                   first.use_graph):
+                raise ValueError("the trainers of a population share max_steps, n_agents and use_graph")
+        self.population = SwarmPopulation.from_engines([t.engine for t in self.trainers])
+
+    def _episode_fn(self, max_steps: int):
+        """DQNTrainer._episode_fn for every member at once: the same per-tick bookkeeping, on
+        [P]-shaped device tensors (a fixed number of launches whatever P is)."""
+        pop = self.population
+        n = self.trainers[0].env.n_agents
+        ctrl_f = pop.ctrl.view(torch.float32)
+        calls = [0]
+
+        def tick():
+            i = calls[0] % max_steps
+            calls[0] += 1
+            pop.train_tick(full_out=False)
+            self._acc_reward.add_(pop.reward[:, :, 0].mean(dim=1) / n)
+            self._acc_loss.add_(ctrl_f[:, 5])
+            self._tick_reward[i].copy_(pop.reward.sum(dim=2).mean(dim=1))
+            self._tick_loss[i].copy_(ctrl_f[:, 5])
+            self._tick_trained[i].copy_(pop.ctrl[:, 7])
+        return tick
+
+    def train_model(self, config):
+        pop, trainers = self.population, self.trainers
+        P, dev = pop.P, pop.device
+        initial_epsilon = config["epsilon"]
+        epsilon_decay = config["epsilon_decay"]
+        min_epsilon = config["min_epsilon"]
+        episodes = config["episodes"]
+        max_steps = trainers[0].env.max_steps or 100
+        epsilon = initial_epsilon
+        self._acc_reward = torch.zeros(P, device=dev)
+        self._acc_loss = torch.zeros(P, device=dev)
+        self._tick_reward = torch.zeros(max_steps, P, device=dev)
+        self._tick_loss = torch.zeros(max_steps, P, device=dev)
+        self._tick_trained = torch.zeros(max_steps, P, dtype=torch.int32, device=dev)
+        tick_fn = self._episode_fn(max_steps)
+        ticks = 0
+        graph = None
+        for episode in range(episodes):
+            pop.reset()
+            pop.set_eps(epsilon)
+            self._acc_reward.zero_()
+            self._acc_loss.zero_()
+            if trainers[0].use_graph and episode > 0:
+                if graph is None:   # episode 0 ran eagerly (warm-up); capture one whole episode once
+                    graph = pop.capture(max_steps, tick_fn)
+                graph.replay()
+            else:
+                for _ in range(max_steps):
+                    tick_fn()
+            epsilon = max(min_epsilon, initial_epsilon * np.exp(-epsilon_decay * episode))
+            # the episode's scalars of every member, read once
+            acc_loss, acc_reward = self._acc_loss.tolist(), self._acc_reward.tolist()
+            rew_t, loss_t, tr_t = self._tick_reward.tolist(), self._tick_loss.tolist(), self._tick_trained.tolist()
+            pop.check_handoffs()
+            for m, t in enumerate(trainers):
+                average_loss = acc_loss[m] / max_steps
+                ep_reward = acc_reward[m]
+                for i in range(max_steps):
+                    t.writer.add_scalar("Reward", rew_t[i][m], ticks + i + 1)
+                    if tr_t[i][m]:
+                        t.writer.add_scalar("Loss", loss_t[i][m], ticks + i + 1)
+                t.episode_losses.append(average_loss)
+                t.rewards_buffer.append(torch.tensor(ep_reward))
+                if (episode + 1) % 10 == 0:
+                    t.episode_rewards.append(sum(t.rewards_buffer) / 10)
+                    t.rewards_buffer = []
+                print(f"Seed {t.seed}, Episode {episode}, Loss: {average_loss}, Reward: {ep_reward * t.env.n_agents}, "
+                      f"Epsilon: {epsilon}")
+            ticks += max_steps
+        print("Training completed")
+        for t in trainers:
+            t._sync_models()
+            os.makedirs(t.models_path, exist_ok=True)
+            torch.save(t.model.state_dict(), f"{t.models_path}/experiment_{t.experiment}-seed_{t.seed}.pth")
+            t.save_metrics_to_csv()
+        print("Models saved successfully!")
 
 
 class SimpleAdamView:

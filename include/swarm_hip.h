@@ -273,6 +273,41 @@ uint32_t swarm_host_sample_position(uint32_t g, uint32_t n, uint32_t k0, uint32_
 int swarm_reduce_advance(const swarm_config* cfg, const swarm_adam_cfg* hp, const float* slabs,
                          const swarm_learner* lr, int32_t replay_capacity, swarm_ctrl* ctrl, void* stream);
 
+/* ---- Population training: P >= 1 independent learners ticked together (the reference runs its
+ * experiment once per seed, train_gcn_dqn.py:262-290; a population runs the seeds side by side).
+ * All members share one swarm_config except the seed (cfg->seed is ignored: each member's own
+ * keys its Philox streams and its replay sampling) and one swarm_adam_cfg.  Each member owns
+ * everything else, named by one descriptor: the arguments swarm_train_tick and
+ * swarm_reduce_advance take for a lone learner.  The caller keeps an array of n_members
+ * descriptors in DEVICE memory, written once.  Members never exchange data: member m computes
+ * bit for bit what a lone learner with that seed computes with swarm_train_tick +
+ * swarm_reduce_advance (tests/test_gpu_population.py). */
+typedef struct swarm_pop_member {
+  uint64_t seed;          /* the member's Philox key (what swarm_config.seed is to a lone learner) */
+  float* state;           /* swarm_state_floats(cfg) floats                                        */
+  swarm_replay replay;    /* the member's ring; replay.capacity is the member's own                */
+  swarm_learner lr;
+  swarm_ctrl* ctrl;
+  swarm_act_out out;      /* any pointer may be NULL                                               */
+  float* slabs;           /* swarm_td_workspace_floats(cfg, hp->batch) floats                      */
+  void* workspace;        /* swarm_train_tick_workspace_bytes(cfg) bytes; zero it with ctrl        */
+  int32_t* sample_out;    /* [hp->batch] this tick's TD batch indices, or NULL                     */
+} swarm_pop_member;
+
+/* The fused training tick of every member in ONE launch, grid (n_act + n_td, n_members): block
+ * (x, m) does for member m what block x of swarm_train_tick does.  The configurations of
+ * swarm_train_tick (else SWARM_E_UNSUPPORTED: n_agents > 16, GAT3, and every other configuration
+ * swarm_train_tick_supported refuses, n_envs < 1 among them); hp->world_size must be 1 and
+ * 1 <= n_members <= 65535 (else SWARM_E_BADARG, as for a NULL cfg, hp or members). */
+int swarm_pop_train_tick(const swarm_config* cfg, const swarm_adam_cfg* hp, const swarm_pop_member* members,
+                         int32_t n_members, void* stream);
+/* swarm_reduce_advance for every member in ONE launch, grid (105 + 1 + 3, n_members): member m's
+ * slabs -> its lr.grad in the same fixed order (+ the clip norm's partials), *_nxt -> *_cur, and
+ * its ctrl advanced with its own sampling key and replay.capacity.  Same checks as
+ * swarm_pop_train_tick. */
+int swarm_pop_reduce_advance(const swarm_config* cfg, const swarm_adam_cfg* hp, const swarm_pop_member* members,
+                             int32_t n_members, void* stream);
+
 /* ---- Peer all-reduce over xGMI (the one exchange of the data-parallel tick).
  * The reference has no distributed code; this replaces the RCCL all_reduce(grad) that would
  * follow swarm_reduce_advance (dist.py allreduce_grad_).  Every rank owns one exchange buffer

@@ -1,0 +1,103 @@
+"""Time a population tick against the same work done one learner at a time.
+
+At the reference's shape (src/training/train_gcn_dqn.py:262-290: 1 env, batch 32, the default
+ring, 100-tick episodes) and P learners (seeds 0..P-1), two ways of running one episode of all P:
+  sequential : P lone SwarmEngines, each replaying its own captured 100-tick episode (hipGraph),
+               one after another on one stream: what running the seeds in turn costs;
+  population : one SwarmPopulation replaying one captured 100-tick episode of all P members.
+Both are timed between two HIP events around `K` back-to-back episode replays (no host
+synchronisation inside), after a warm-up of both that also fills the replay rings past the batch
+size, so every timed tick trains.  The two alternate, `--repeats` times each; the table gives the
+median and the spread in us per population tick (= one tick of all P learners).  Environment
+resets are not timed (they are per-member launches in both).
+
+usage: python tools/pop_time.py [--repeats 7] [--sizes 1,10,64] [--out population_time.json]
+Prints one JSON line per configuration and population size.
+"""
+import argparse
+import json
+import math
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import swarm_amd  # noqa: E402
+import swarm_amd._lib as L  # noqa: E402
+
+CONFIGS = (("GoTo", 5), ("GoTo", 10), ("ObstacleAvoidance", 5), ("ObstacleAvoidance", 10))
+TICKS = 100
+
+
+def window_us(replay, episodes):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(episodes):
+        replay()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) * 1e3 / (episodes * TICKS)
+
+
+def measure(scen, N, P, repeats):
+    kw = dict(scenario=scen, n_agents=N, n_envs=1, batch=32, eps=0.05, shared_reset=True)
+    lone = [swarm_amd.SwarmEngine(seed=s, **kw) for s in range(P)]
+    pop = swarm_amd.SwarmPopulation(seeds=list(range(P)), **kw)
+    for e in lone:
+        e.reset(0)
+    pop.reset(0)
+    lone_graphs = [e.capture(TICKS) for e in lone]
+    pop_graph = pop.capture(TICKS)
+
+    def sequential():
+        for g in lone_graphs:
+            g.replay()
+
+    ways = {"sequential": sequential, "population": pop_graph.replay}
+    # enough episodes per window that it lasts tens of milliseconds at least
+    episodes = {"sequential": max(2, math.ceil(40 / P)), "population": 40}
+    for k, fn in ways.items():   # warm-up: code objects loaded, rings past the batch size, clocks up
+        window_us(fn, 2)
+    times = {k: [] for k in ways}
+    for _ in range(repeats):
+        for k, fn in ways.items():
+            times[k].append(window_us(fn, episodes[k]))
+    torch.cuda.synchronize()
+    pop.check_handoffs()
+    for e in lone:
+        e.check_handoffs()
+    steps = [c["adam_step"] for c in pop.read_ctrl()]
+    assert min(steps) > 0, "the timed ticks did not train"
+    out = {"scenario": scen, "n_agents": N, "n_envs": 1, "batch": 32, "population": P, "ticks_per_episode": TICKS,
+           "episodes_per_window": episodes, "repeats": repeats, "build": pop.lib.swarm_build_info().decode()}
+    for k, v in times.items():
+        out[k + "_us_per_tick"] = round(statistics.median(v), 3)
+        out[k + "_us_min_max"] = [round(min(v), 3), round(max(v), 3)]
+    out["sequential_over_population"] = round(out["sequential_us_per_tick"] / out["population_us_per_tick"], 3)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--sizes", default="1,10,64")
+    ap.add_argument("--configs", default=None, help="e.g. GoTo:5,ObstacleAvoidance:10 (default: all four)")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    configs = CONFIGS if not a.configs else tuple((c.split(":")[0], int(c.split(":")[1])) for c in a.configs.split(","))
+    rows = []
+    for scen, N in configs:
+        for P in [int(x) for x in a.sizes.split(",")]:
+            rows.append(measure(scen, N, P, a.repeats))
+            print(json.dumps(rows[-1]), flush=True)
+            if a.out:
+                os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+                with open(a.out, "w") as f:
+                    json.dump(rows, f, indent=1)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

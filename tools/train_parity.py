@@ -16,6 +16,10 @@ the N the recorded runs used.  ``--agents`` sweeps it.
 
     python tools/train_parity.py [--out out.json] [--seeds 0,1,...] [--episodes 1000]
                                  [--scenarios GoTo,ObstacleAvoidance] [--agents 10[,5,...]]
+                                 [--population]
+
+``--population`` trains the seeds of a scenario and agent count together (PopulationTrainer: one
+launch ticks every seed) instead of one after another; the curves are the same bits.
 """
 import argparse
 import contextlib
@@ -43,6 +47,24 @@ def run(scen_name, seed, episodes, n_agents=10):
         with contextlib.redirect_stdout(io.StringIO()):
             tr.train_model({"epsilon": 0.99, "epsilon_decay": 0.01, "min_epsilon": 0.05, "episodes": episodes})
     return [float(x) for x in tr.episode_rewards]
+
+
+def run_population(scen_name, seeds, episodes, n_agents=10):
+    """run() for all seeds at once: {seed: curve}"""
+    import swarm_amd
+    with tempfile.TemporaryDirectory() as d:
+        trainers = []
+        for seed in seeds:
+            scen = swarm_amd.GoToPositionScenario() if scen_name == "GoTo" else swarm_amd.ObstacleAvoidanceScenario()
+            env = swarm_amd.make_env(scenario=scen, num_envs=1, continuous_actions=False, wrapper=None, max_steps=100,
+                                     dict_spaces=True, n_agents=n_agents, seed=seed)
+            swarm_amd.set_seed(seed)
+            trainers.append(swarm_amd.DQNTrainer(env, seed, os.path.join(d, "models"), os.path.join(d, "stats"),
+                                                 scen_name))
+        with contextlib.redirect_stdout(io.StringIO()):
+            swarm_amd.PopulationTrainer(trainers).train_model(
+                {"epsilon": 0.99, "epsilon_decay": 0.01, "min_epsilon": 0.05, "episodes": episodes})
+    return {t.seed: [float(x) for x in t.episode_rewards] for t in trainers}
 
 
 def welch(a, b):
@@ -95,6 +117,7 @@ def main():
     ap.add_argument("--episodes", type=int, default=1000)
     ap.add_argument("--scenarios", default="GoTo,ObstacleAvoidance")
     ap.add_argument("--agents", default="10")
+    ap.add_argument("--population", action="store_true", help="train the seeds together (PopulationTrainer)")
     a = ap.parse_args()
     seeds = [int(s) for s in a.seeds.split(",")]
     ref = json.load(open(os.path.join(ROOT, "tests", "golden", "train_stats.json")))
@@ -102,10 +125,11 @@ def main():
     for scen in a.scenarios.split(","):
         for n in [int(x) for x in a.agents.split(",")]:
             t0 = time.time()
-            ours = {s: run(scen, s, a.episodes, n) for s in seeds}
+            ours = (run_population(scen, seeds, a.episodes, n) if a.population
+                    else {s: run(scen, s, a.episodes, n) for s in seeds})
             secs = time.time() - t0
             r = compare(ref, scen, ours, seeds, a.episodes)
-            r |= {"scenario": scen, "n_agents": n, "seconds": secs, "ticks": len(seeds) * a.episodes * 100,
+            r |= {"scenario": scen, "n_agents": n, "seconds": secs, "population": bool(a.population), "ticks": len(seeds) * a.episodes * 100,
                   "curves": {str(s): ours[s] for s in seeds}}
             res["runs"].append(r)
             w = r.get("last100_welch", {})
