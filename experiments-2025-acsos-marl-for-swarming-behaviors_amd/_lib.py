@@ -77,53 +77,60 @@ class SwarmPeer(ctypes.Structure):
                 ("err", c_void_p), ("timeout_us", c_uint32), ("pad", c_int32)]
 
 
-# swarm_ctrl is 16 x 4-byte words on the device; field -> word index
+# swarm_ctrl is CTRL_WORDS 4-byte words on the device; field -> word index
 CTRL_WORDS = 32
 CTRL = dict(tick=0, write_slot=1, filled_slots=2, adam_step=3, eps=4, loss=5, grad_norm=6, trained=7, episode=8,
             adam_step_size=14, adam_inv_bc2=15, peer_hold=23, one_m_beta1=24, one_m_beta2=25)
+
+
+
+class c_stream(c_void_p):
+    """The `void* stream` that ends a launching entry point's parameters: ``call`` fills it in."""
+    from_param = c_void_p.from_param   # a direct caller passes whatever a void* parameter takes
+
 
 _PROTOS = {
     "swarm_abi_version": (c_int32, []),
     "swarm_n_params": (c_int32, []),
     "swarm_build_info": (ctypes.c_char_p, []),
     "swarm_state_floats": (c_int64, [POINTER(SwarmConfig)]),
-    "swarm_env_reset": (c_int32, [POINTER(SwarmConfig), c_void_p, c_uint32, c_void_p]),
-    "swarm_env_sync_state": (c_int32, [POINTER(SwarmConfig), c_void_p, c_int32, c_void_p]),
-    "swarm_env_step": (c_int32, [POINTER(SwarmConfig), c_void_p, c_void_p, POINTER(SwarmActOut), c_void_p]),
-    "swarm_build_graph": (c_int32, [POINTER(SwarmConfig), c_void_p, c_void_p, c_void_p]),
-    "swarm_edges_to_mult": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
-    "swarm_q_forward": (c_int32, [POINTER(SwarmConfig), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "swarm_env_reset": (c_int32, [POINTER(SwarmConfig), c_void_p, c_uint32, c_stream]),
+    "swarm_env_sync_state": (c_int32, [POINTER(SwarmConfig), c_void_p, c_int32, c_stream]),
+    "swarm_env_step": (c_int32, [POINTER(SwarmConfig), c_void_p, c_void_p, POINTER(SwarmActOut), c_stream]),
+    "swarm_build_graph": (c_int32, [POINTER(SwarmConfig), c_void_p, c_void_p, c_stream]),
+    "swarm_edges_to_mult": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_stream]),
+    "swarm_q_forward": (c_int32, [POINTER(SwarmConfig), c_void_p, c_void_p, c_void_p, c_void_p, c_stream]),
     "swarm_q_backward": (c_int32, [POINTER(SwarmConfig), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                   c_void_p]),
+                                   c_stream]),
     "swarm_act_step": (c_int32, [POINTER(SwarmConfig), c_void_p, c_void_p, POINTER(SwarmReplay), c_void_p,
-                                 POINTER(SwarmActOut), c_void_p]),
+                                 POINTER(SwarmActOut), c_stream]),
     "swarm_train_act_step": (c_int32, [POINTER(SwarmConfig), POINTER(SwarmAdamCfg), POINTER(SwarmLearner), c_void_p,
-                                       POINTER(SwarmReplay), c_void_p, POINTER(SwarmActOut), c_void_p, c_void_p]),
+                                       POINTER(SwarmReplay), c_void_p, POINTER(SwarmActOut), c_void_p, c_stream]),
     "swarm_reduce_advance": (c_int32, [POINTER(SwarmConfig), POINTER(SwarmAdamCfg), c_void_p, POINTER(SwarmLearner),
-                                       c_int32, c_void_p, c_void_p]),
+                                       c_int32, c_void_p, c_stream]),
     "swarm_sample_prepare": (c_int32, [POINTER(SwarmConfig), POINTER(SwarmAdamCfg), c_int32, c_void_p, c_void_p,
-                                       c_void_p]),
+                                       c_stream]),
     "swarm_adam_flush": (c_int32, [POINTER(SwarmConfig), POINTER(SwarmAdamCfg), POINTER(SwarmLearner), c_void_p,
-                                   c_void_p]),
+                                   c_stream]),
     "swarm_rollout": (c_int32, [POINTER(SwarmConfig), c_void_p, c_void_p, c_int32, c_uint32, c_float,
-                                POINTER(SwarmActOut), c_void_p]),
+                                POINTER(SwarmActOut), c_stream]),
     "swarm_td_workspace_floats": (c_int64, [POINTER(SwarmConfig), c_int32]),
     "swarm_td_grad": (c_int32, [POINTER(SwarmConfig), POINTER(SwarmAdamCfg), c_void_p, c_void_p,
-                                POINTER(SwarmReplay), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "swarm_grad_reduce": (c_int32, [POINTER(SwarmConfig), POINTER(SwarmAdamCfg), c_void_p, c_void_p, c_void_p]),
+                                POINTER(SwarmReplay), c_void_p, c_void_p, c_void_p, c_void_p, c_stream]),
+    "swarm_grad_reduce": (c_int32, [POINTER(SwarmConfig), POINTER(SwarmAdamCfg), c_void_p, c_void_p, c_stream]),
     "swarm_adam_step": (c_int32, [POINTER(SwarmConfig), POINTER(SwarmAdamCfg), c_void_p, c_void_p, c_void_p,
-                                  c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
-    "swarm_ctrl_init": (c_int32, [POINTER(SwarmAdamCfg), c_float, c_void_p, c_void_p]),
-    "swarm_ctrl_advance": (c_int32, [POINTER(SwarmConfig), POINTER(SwarmReplay), c_void_p, c_void_p]),
+                                  c_void_p, c_void_p, c_int32, c_void_p, c_stream]),
+    "swarm_ctrl_init": (c_int32, [POINTER(SwarmAdamCfg), c_float, c_void_p, c_stream]),
+    "swarm_ctrl_advance": (c_int32, [POINTER(SwarmConfig), POINTER(SwarmReplay), c_void_p, c_stream]),
     "swarm_host_topk_set": (c_int32, [POINTER(c_float), c_int32, c_int32, POINTER(ctypes.c_uint8)]),
     "swarm_train_tick_supported": (c_int32, [POINTER(SwarmConfig)]),
     "swarm_train_tick_workspace_bytes": (c_int64, [POINTER(SwarmConfig)]),
     "swarm_train_tick": (c_int32, [POINTER(SwarmConfig), POINTER(SwarmAdamCfg), POINTER(SwarmLearner), c_void_p,
                                    POINTER(SwarmReplay), c_void_p, POINTER(SwarmActOut), c_void_p, c_void_p,
-                                   c_void_p, c_void_p]),
-    "swarm_pop_train_tick": (c_int32, [POINTER(SwarmConfig), POINTER(SwarmAdamCfg), c_void_p, c_int32, c_void_p]),
+                                   c_void_p, c_stream]),
+    "swarm_pop_train_tick": (c_int32, [POINTER(SwarmConfig), POINTER(SwarmAdamCfg), c_void_p, c_int32, c_stream]),
     "swarm_pop_reduce_advance": (c_int32, [POINTER(SwarmConfig), POINTER(SwarmAdamCfg), c_void_p, c_int32,
-                                           c_void_p]),
+                                           c_stream]),
     "swarm_peer_buffer_bytes": (c_int64, []),
     "swarm_peer_alloc": (c_int32, [POINTER(c_void_p)]),
     "swarm_peer_free": (c_int32, [c_void_p]),
@@ -131,8 +138,8 @@ _PROTOS = {
     "swarm_peer_ipc_open": (c_int32, [c_void_p, POINTER(c_void_p)]),
     "swarm_peer_ipc_close": (c_int32, [c_void_p]),
     "swarm_reduce_advance_peer": (c_int32, [POINTER(SwarmConfig), POINTER(SwarmAdamCfg), c_void_p,
-                                            POINTER(SwarmLearner), c_int32, c_void_p, POINTER(SwarmPeer), c_void_p]),
-    "swarm_peer_allreduce": (c_int32, [POINTER(SwarmPeer), c_void_p, c_int32, c_void_p]),
+                                            POINTER(SwarmLearner), c_int32, c_void_p, POINTER(SwarmPeer), c_stream]),
+    "swarm_peer_allreduce": (c_int32, [POINTER(SwarmPeer), c_void_p, c_int32, c_stream]),
     "swarm_host_sample_index": (c_uint32, [c_uint32, c_uint32, c_uint32, c_uint32, c_uint32]),
     "swarm_host_sample_position": (c_uint32, [c_uint32, c_uint32, c_uint32, c_uint32, c_uint32]),
 }
@@ -141,31 +148,9 @@ EXPORTED = tuple(_PROTOS)
 _lib = None
 
 
-def load(require_gpu: bool = True):
-    """Load the library (once).  Raises if it was not built or no GPU is visible."""
-    global _lib
-    if require_gpu and not torch.cuda.is_available():
-        raise RuntimeError("libswarm_hip: no ROCm GPU visible (torch.cuda.is_available() is False); "
-                           "this framework has no CPU fallback")
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(f"libswarm_hip.so not built at {LIB_PATH}; run __graft_entry__.build()")
-        lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in _PROTOS.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        if lib.swarm_abi_version() != ABI_VERSION:
-            raise RuntimeError("libswarm_hip ABI mismatch")
-        _lib = lib
-    return _lib
-
-
-def load_variant(path: str):
-    """A second build of the library (e.g. build.HODROP_OUT, the hand-off overrun test
-    library) with the same prototypes, loaded beside the main one; for tests."""
+def _open(path: str):
     if not os.path.exists(path):
-        raise RuntimeError(f"{path} not built; run __graft_entry__.build()")
+        raise RuntimeError(f"{os.path.basename(path)} not built at {path}; run __graft_entry__.build()")
     lib = ctypes.CDLL(path)
     for name, (res, args) in _PROTOS.items():
         fn = getattr(lib, name)
@@ -176,10 +161,49 @@ def load_variant(path: str):
     return lib
 
 
+def load(require_gpu: bool = True):
+    """Load the library (once).  Raises if it was not built or no GPU is visible."""
+    global _lib
+    if require_gpu and not torch.cuda.is_available():
+        raise RuntimeError("libswarm_hip: no ROCm GPU visible (torch.cuda.is_available() is False); "
+                           "this framework has no CPU fallback")
+    if _lib is None:
+        _lib = _open(LIB_PATH)
+    return _lib
+
+
+def load_variant(path: str):
+    """A second build of the library (e.g. build.HODROP_OUT, the hand-off overrun test
+    library) with the same prototypes, loaded beside the main one; for tests."""
+    return _open(path)
+
+
 def check(rc: int, what: str):
     if rc != 0:
         msg = ERRORS.get(rc, f"hipError_t {rc}")
         raise RuntimeError(f"{what} failed: {msg}")
+
+
+def ref(obj):
+    """A ctypes structure by reference; anything else (None = NULL, addresses, numbers) as it is."""
+    return ctypes.byref(obj) if isinstance(obj, ctypes.Structure) else obj
+
+
+def call(lib, name: str, *args):
+    """Call the status-returning entry point ``name``: structures go by reference, None as NULL,
+    torch's current stream is appended where the entry point takes one, and a status other than
+    0 raises with the entry point's name."""
+    args = [ref(a) for a in args]
+    if _PROTOS[name][1][-1:] == [c_stream]:
+        args.append(stream_ptr())
+    check(getattr(lib, name)(*args), name)
+
+
+def size(lib, name: str, *args) -> int:
+    """Call a size-returning entry point (as ``call``, no stream); a negative size is its status."""
+    n = int(getattr(lib, name)(*[ref(a) for a in args]))
+    check(min(n, 0), name)
+    return n
 
 
 def ptr(t) -> int:

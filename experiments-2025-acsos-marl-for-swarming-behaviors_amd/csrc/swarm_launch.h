@@ -142,4 +142,22 @@ struct TdSpecs {
   static constexpr bool allows(int sp) { return spec_complete(sp); }
 };
 
+// ---- the fused tick's launch (tick_kernel in swarm_tick.hip; pop_tick_kernel, one learner per
+// blockIdx.y, in swarm_pop.hip)
+// workspace: [err: 1 u32, padded to kTickErrBytes], then the tagged hand-off records
+constexpr int kTickErrBytes = 512;
+// the grid's x extent: acting blocks first, then one TD block per slab
+inline int tick_grid_x(int n_envs, int n_slabs) { return (n_envs + kActWPB - 1) / kActWPB + n_slabs; }
+// (N, scenario, graph, conv) -> f(NSA, SCEN, SPEC) of the tick instance (TickSpecs); the caller's
+// kernel template takes <NSA, td_wave_slots(NSA), NSA, SCEN, SPEC>
+template <class F>
+void with_tick_instance(const swarm_config* c, F&& f) {
+  with_slots<8, 16>(c->n_agents, [&](auto ns) {
+    with_scenario(c->scenario, [&](auto sc) {
+      with_spec<TickSpecs<decltype(ns)::value, decltype(sc)::value>>(c->graph, c->conv,
+                                                                     [&](auto sp) { f(ns, sc, sp); });
+    });
+  });
+}
+
 }  // namespace swarm

@@ -71,9 +71,6 @@ __device__ inline swarm_pop_member load_member(const swarm_pop_member* __restric
 }
 __device__ inline uint32_t member_k0(const swarm_pop_member& M) { return (uint32_t)(M.seed & 0xFFFFFFFFu); }
 __device__ inline uint32_t member_k1(const swarm_pop_member& M) { return (uint32_t)(M.seed >> 32); }
-// the member's fused-tick workspace: [err: 1 u32, padded to 512 B], then the hand-off records
-// (swarm_train_tick_workspace_bytes; the layout of swarm_tick.hip)
-constexpr int kPopErrBytes = 512;
 
 // A, T, X: the arguments of tick_kernel (swarm_tick.hip) with every per-member field left empty.
 // Same block shape and occupancy target as tick_kernel.
@@ -87,7 +84,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GS == 8 ? 2
   const swarm_learner lr = M.lr;
   const swarm_replay replay = M.replay;
   char* const ws = static_cast<char*>(M.workspace);
-  unsigned long long* const rec = reinterpret_cast<unsigned long long*>(ws + kPopErrBytes);
+  // the member's fused-tick workspace: the error word's region, then the hand-off records (swarm_launch.h)
+  unsigned long long* const rec = reinterpret_cast<unsigned long long*>(ws + kTickErrBytes);
   const int n_act = (B + kActWPB - 1) / kActWPB;
   if ((int)blockIdx.x < n_act) {
     ActArgs a = A;
@@ -153,16 +151,12 @@ int swarm_pop_train_tick(const swarm_config* cfg, const swarm_adam_cfg* hp, cons
   t.k0 = 0; t.k1 = 0;
   TdFused x = {};
   x.hp = *hp;
-  // per member: acting blocks first, then one TD block per slab; the kernel set of the fused tick
-  const dim3 grid((B + kActWPB - 1) / kActWPB + t.n_slabs, n_members), block(256);
-  with_slots<8, 16>(N, [&](auto ns) {
-    with_scenario(cfg->scenario, [&](auto sc) {
-      constexpr int NSA = decltype(ns)::value, SC = decltype(sc)::value;
-      with_spec<TickSpecs<NSA, SC>>(cfg->graph, cfg->conv, [&](auto sp) {
-        hipLaunchKernelGGL((pop_tick_kernel<NSA, td_wave_slots(NSA), NSA, SC, decltype(sp)::value>), grid, block, 0,
-                           (hipStream_t)stream, members, B, N, a, t, x);
-      });
-    });
+  // per member the lone tick's grid; the kernel set of the fused tick
+  const dim3 grid(tick_grid_x(B, t.n_slabs), n_members), block(256);
+  with_tick_instance(cfg, [&](auto ns, auto sc, auto sp) {
+    constexpr int NSA = decltype(ns)::value;
+    hipLaunchKernelGGL((pop_tick_kernel<NSA, td_wave_slots(NSA), NSA, decltype(sc)::value, decltype(sp)::value>), grid,
+                       block, 0, (hipStream_t)stream, members, B, N, a, t, x);
   });
   return (int)hipGetLastError();
 }
@@ -173,8 +167,8 @@ int swarm_pop_reduce_advance(const swarm_config* cfg, const swarm_adam_cfg* hp, 
   ReduceArgs a = {};
   a.n_slabs = diag_reduce_slabs(td_blocks(cfg->n_agents, hp->batch));
   a.advance = 1; a.B = cfg->n_envs; a.N = cfg->n_agents; a.batch = hp->batch; a.hp = *hp;
-  hipLaunchKernelGGL(pop_reduce_kernel, dim3(kRedColBlocks + 1 + kRedCopyBlocks, n_members),
-                     dim3(kRedCols * kRedGroups), 0, (hipStream_t)stream, members, a.n_slabs, cfg->env_offset, a);
+  hipLaunchKernelGGL(pop_reduce_kernel, dim3(reduce_grid_x(a.advance), n_members), dim3(kRedCols * kRedGroups), 0,
+                     (hipStream_t)stream, members, a.n_slabs, cfg->env_offset, a);
   return (int)hipGetLastError();
 }
 

@@ -43,6 +43,8 @@ constexpr int kRedRuns = kRedGroups / 8;
 constexpr int kRedChunk = 8;      // slabs per load chunk of a group
 constexpr int kRedColBlocks = (N_PARAMS + 1 + kRedCols - 1) / kRedCols;
 constexpr int kRedCopyBlocks = 3;
+// a reduce launch's grid: the column blocks; advance mode adds the control block and the copy blocks
+constexpr int reduce_grid_x(int advance) { return kRedColBlocks + (advance ? 1 + kRedCopyBlocks : 0); }
 
 // ---- the ctrl advance of one tick (the reduce launch's control block).  Every thread of the
 //      block calls it; thread 0 advances the counters and the Adam scalars, thread 64 derives the

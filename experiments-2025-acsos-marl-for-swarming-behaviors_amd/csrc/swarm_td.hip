@@ -33,6 +33,13 @@ __global__ __launch_bounds__(kRedCols * kRedGroups) void grad_reduce_kernel(cons
                                                                             int n_slabs, int advance, ReduceArgs A) {
 #include "swarm_reduce_body.h"
 }
+// the one launch of grad_reduce_kernel: grid (reduce_grid_x, swarm_reduce.h), block, argument order
+template <int PEER>
+static int launch_reduce(const ReduceArgs& a, void* stream) {
+  hipLaunchKernelGGL(grad_reduce_kernel<PEER>, dim3(reduce_grid_x(a.advance)), dim3(kRedCols * kRedGroups), 0,
+                     (hipStream_t)stream, a.slabs, a.ctrl, a.n_slabs, a.advance, a);
+  return (int)hipGetLastError();
+}
 
 // ---------------------------------------------------------------- clip + Adam + target sync
 // Unfused path (swarm_adam_step): apply now, then advance ctrl.  Flush path
@@ -160,9 +167,7 @@ int swarm_grad_reduce(const swarm_config* cfg, const swarm_adam_cfg* hp, const f
   if (int e = check_td(cfg, hp)) return e;
   ReduceArgs a = {};
   a.n_slabs = td_blocks(cfg->n_agents, hp->batch); a.slabs = slabs; a.grad = grad;
-  hipLaunchKernelGGL(grad_reduce_kernel<0>, dim3(kRedColBlocks), dim3(kRedCols * kRedGroups), 0,
-                     (hipStream_t)stream, a.slabs, a.ctrl, a.n_slabs, a.advance, a);
-  return (int)hipGetLastError();
+  return launch_reduce<0>(a, stream);
 }
 
 // GCN.forward's backward for a caller's dL/dQ (swarm_qbk.h; kernels in swarm_qbk.hip), then the
@@ -179,9 +184,7 @@ int swarm_q_backward(const swarm_config* cfg, const float* params, const float* 
   if (int e = qbk_launch(q, (hipStream_t)stream)) return e;
   ReduceArgs a = {};
   a.n_slabs = q.n_slabs; a.slabs = workspace; a.grad = grad;
-  hipLaunchKernelGGL(grad_reduce_kernel<0>, dim3(kRedColBlocks), dim3(kRedCols * kRedGroups), 0,
-                     (hipStream_t)stream, a.slabs, a.ctrl, a.n_slabs, a.advance, a);
-  return (int)hipGetLastError();
+  return launch_reduce<0>(a, stream);
 }
 
 static int reduce_advance(const swarm_config* cfg, const swarm_adam_cfg* hp, const float* slabs, const swarm_learner* lr,
@@ -195,13 +198,7 @@ static int reduce_advance(const swarm_config* cfg, const swarm_adam_cfg* hp, con
   a.capacity = replay_capacity; a.B = cfg->n_envs; a.N = cfg->n_agents; a.batch = hp->batch;
   a.hp = *hp;
   a.k0 = sample_salt_k0(seed_k0(cfg), cfg->env_offset); a.k1 = seed_k1(cfg);
-  if (peer)
-    hipLaunchKernelGGL(grad_reduce_kernel<1>, dim3(kRedColBlocks + 1 + kRedCopyBlocks), dim3(kRedCols * kRedGroups), 0,
-                       (hipStream_t)stream, a.slabs, a.ctrl, a.n_slabs, a.advance, a);
-  else
-    hipLaunchKernelGGL(grad_reduce_kernel<0>, dim3(kRedColBlocks + 1 + kRedCopyBlocks), dim3(kRedCols * kRedGroups), 0,
-                       (hipStream_t)stream, a.slabs, a.ctrl, a.n_slabs, a.advance, a);
-  return (int)hipGetLastError();
+  return peer ? launch_reduce<1>(a, stream) : launch_reduce<0>(a, stream);
 }
 
 int swarm_reduce_advance(const swarm_config* cfg, const swarm_adam_cfg* hp, const float* slabs, const swarm_learner* lr,

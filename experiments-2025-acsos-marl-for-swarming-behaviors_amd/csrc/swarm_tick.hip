@@ -52,8 +52,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GS == 8 ? 2
 using namespace swarm;
 
 namespace {
-// workspace: [err: 1 u32, padded to 512 B], then the tagged hand-off records
-size_t err_bytes() { return 512; }
+// the workspace's hand-off records, after its error word's region (kTickErrBytes, swarm_launch.h)
 size_t rec_bytes(int B, int N) { return (size_t)B * ho_stride_granules(N) * 8; }
 }  // namespace
 
@@ -63,7 +62,7 @@ int swarm_train_tick_supported(const swarm_config* cfg) { return check_config(cf
 
 int64_t swarm_train_tick_workspace_bytes(const swarm_config* cfg) {
   if (!swarm_train_tick_supported(cfg)) return SWARM_E_UNSUPPORTED;
-  return (int64_t)(err_bytes() + rec_bytes(cfg->n_envs, cfg->n_agents));
+  return (int64_t)(kTickErrBytes + rec_bytes(cfg->n_envs, cfg->n_agents));
 }
 
 int swarm_train_tick(const swarm_config* cfg, const swarm_adam_cfg* hp, const swarm_learner* lr, float* state,
@@ -76,7 +75,7 @@ int swarm_train_tick(const swarm_config* cfg, const swarm_adam_cfg* hp, const sw
   const int B = cfg->n_envs, N = cfg->n_agents;
   char* ws = static_cast<char*>(workspace);
   uint32_t* err = reinterpret_cast<uint32_t*>(ws);
-  unsigned long long* rec = reinterpret_cast<unsigned long long*>(ws + err_bytes());
+  unsigned long long* rec = reinterpret_cast<unsigned long long*>(ws + kTickErrBytes);
 
   ActArgs a = make_act_args(cfg);
   a.state = state; a.ctrl = ctrl; a.learn = 1; a.lr = *lr; a.hp = *hp; a.sample_out = nullptr;
@@ -90,16 +89,12 @@ int swarm_train_tick(const swarm_config* cfg, const swarm_adam_cfg* hp, const sw
   TdFused x = {};
   x.lr = *lr; x.hp = *hp; x.ho_rec = rec; x.ho_err = err;
 
-  // acting blocks first, then one TD block per slab; which tick_kernel: TickSpecs (swarm_launch.h)
-  const dim3 grid((B + kActWPB - 1) / kActWPB + t.n_slabs), block(256);
-  with_slots<8, 16>(N, [&](auto ns) {
-    with_scenario(cfg->scenario, [&](auto sc) {
-      constexpr int NSA = decltype(ns)::value, SC = decltype(sc)::value;
-      with_spec<TickSpecs<NSA, SC>>(cfg->graph, cfg->conv, [&](auto sp) {
-        hipLaunchKernelGGL((tick_kernel<NSA, td_wave_slots(NSA), NSA, SC, decltype(sp)::value>), grid, block, 0,
-                           (hipStream_t)stream, ctrl, state, lr->grad, lr->w_cur, lr->m_cur, lr->v_cur, B, N, a, t, x);
-      });
-    });
+  const dim3 grid(tick_grid_x(B, t.n_slabs)), block(256);
+  with_tick_instance(cfg, [&](auto ns, auto sc, auto sp) {
+    constexpr int NSA = decltype(ns)::value;
+    hipLaunchKernelGGL((tick_kernel<NSA, td_wave_slots(NSA), NSA, decltype(sc)::value, decltype(sp)::value>), grid,
+                       block, 0, (hipStream_t)stream, ctrl, state, lr->grad, lr->w_cur, lr->m_cur, lr->v_cur, B, N, a, t,
+                       x);
   });
   return (int)hipGetLastError();
 }

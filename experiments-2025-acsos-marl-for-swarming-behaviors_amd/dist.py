@@ -101,10 +101,10 @@ class PeerExchange:
     # ------------------------------------------------------------------ construction
     @staticmethod
     def _alloc(lib) -> int:
-        from ._lib import c_void_p, check
+        from ._lib import c_void_p, call
         import ctypes
         p = c_void_p()
-        check(lib.swarm_peer_alloc(ctypes.byref(p)), "swarm_peer_alloc")
+        call(lib, "swarm_peer_alloc", ctypes.byref(p))
         return int(p.value)
 
     @classmethod
@@ -128,7 +128,7 @@ class PeerExchange:
         try:
             own = cls._alloc(lib)
             h = (ctypes.c_char * _lib.PEER_HANDLE_BYTES)()
-            _lib.check(lib.swarm_peer_ipc_handle(ctypes.c_void_p(own), h), "swarm_peer_ipc_handle")
+            _lib.call(lib, "swarm_peer_ipc_handle", ctypes.c_void_p(own), h)
             mine = bytes(h)
         except RuntimeError as e:   # keep going: this rank still joins the gather and the barrier
             err = e
@@ -146,9 +146,9 @@ class PeerExchange:
             p = ctypes.c_void_p()
             buf = (ctypes.c_char * _lib.PEER_HANDLE_BYTES).from_buffer_copy(hq)
             try:
-                _lib.check(lib.swarm_peer_ipc_open(buf, ctypes.byref(p)), f"swarm_peer_ipc_open(rank {q})")
+                _lib.call(lib, "swarm_peer_ipc_open", buf, ctypes.byref(p))
             except RuntimeError as e:   # keep going: every rank must still reach the barrier below
-                err = err or e
+                err = err or RuntimeError(f"{e} (the buffer of rank {q})")
                 recv.append(None)
                 continue
             recv.append(int(p.value))
@@ -193,12 +193,10 @@ class PeerExchange:
     def allreduce_(self, x: torch.Tensor) -> torch.Tensor:
         """In-place rank-ordered SUM of a flat fp32 device tensor (<= 1,674 elements), launched on
         the current stream, which must be this rank's one peer stream (``check_stream``)."""
-        from ._lib import check, stream_ptr
-        import ctypes
+        from ._lib import call
         assert x.is_contiguous() and x.dtype == torch.float32 and x.device == self.device
         self.check_stream()
-        check(self.lib.swarm_peer_allreduce(ctypes.byref(self.struct), x.data_ptr(), x.numel(), stream_ptr()),
-              "swarm_peer_allreduce")
+        call(self.lib, "swarm_peer_allreduce", self.struct, x.data_ptr(), x.numel())
         return x
 
     def errors(self) -> int:
@@ -239,10 +237,9 @@ class PeerExchange:
         holds must equal their rank-ordered fp32 sum bit for bit; the expired-wait word, the
         hand-off word and ctrl.peer_hold must stay 0.  Collective: every rank calls it.  Returns
         {"ok": bool, ...details}; the caller MIN-reduces "ok" over the ranks and falls back."""
-        import ctypes
         import torch.distributed as dist
         from . import _lib
-        from ._lib import CTRL, N_PARAMS, check, ptr, stream_ptr
+        from ._lib import CTRL, N_PARAMS, call, ptr
         if self.error is not None:
             return {"ok": False, "why": str(self.error)}
         eng = make_engine(self)
@@ -256,8 +253,7 @@ class PeerExchange:
             eng.reset(0)
             for t in range(ticks):
                 eng.train_tick()
-                check(self.lib.swarm_grad_reduce(ctypes.byref(eng.cfg), ctypes.byref(eng.hp), ptr(eng.slabs),
-                                                 ptr(local), stream_ptr()), "swarm_grad_reduce")
+                call(self.lib, "swarm_grad_reduce", eng.cfg, eng.hp, ptr(eng.slabs), ptr(local))
                 torch.cuda.synchronize(self.device)
                 mine = local[:N_PARAMS + 1].clone()
                 allv = [torch.zeros_like(mine, device=dev) for _ in range(self.world_size)]
@@ -279,10 +275,10 @@ class PeerExchange:
         return out
 
     def close(self):
-        from ._lib import check
+        from ._lib import call
         import ctypes
         for p in self._mapped:
-            check(self.lib.swarm_peer_ipc_close(ctypes.c_void_p(p)), "swarm_peer_ipc_close")
+            call(self.lib, "swarm_peer_ipc_close", ctypes.c_void_p(p))
         for p in self._owned:
-            check(self.lib.swarm_peer_free(ctypes.c_void_p(p)), "swarm_peer_free")
+            call(self.lib, "swarm_peer_free", ctypes.c_void_p(p))
         self._mapped, self._owned = [], []

@@ -173,60 +173,13 @@ class DQNTrainer:
             self._tick_trained[i].copy_(eng.ctrl[7])
         return tick
 
+    def _check_episode(self):
+        self.engine.check_handoffs()   # an overrun hand-off dropped TD graphs: fail loudly (one 4-byte read)
+        if self.engine.peer is not None:
+            self.engine.peer.check()   # an expired peer-exchange wait: the summed gradient is wrong
+
     def train_model(self, config):
-        eng = self.engine
-        initial_epsilon = config["epsilon"]
-        epsilon_decay = config["epsilon_decay"]
-        min_epsilon = config["min_epsilon"]
-        episodes = config["episodes"]
-        max_steps = self.env.max_steps or 100
-        epsilon = initial_epsilon
-        self._acc_reward = torch.zeros((), device=eng.device)
-        self._acc_loss = torch.zeros((), device=eng.device)
-        self._tick_reward = torch.zeros(max_steps, device=eng.device)
-        self._tick_loss = torch.zeros(max_steps, device=eng.device)
-        self._tick_trained = torch.zeros(max_steps, dtype=torch.int32, device=eng.device)
-        tick_fn = self._episode_fn(max_steps)
-        ticks = 0
-        graph = None
-        for episode in range(episodes):
-            eng.reset()
-            eng.set_eps(epsilon)
-            self._acc_reward.zero_()
-            self._acc_loss.zero_()
-            if self.use_graph and episode > 0:
-                if graph is None:   # episode 0 ran eagerly (warm-up); capture one whole episode once
-                    graph = eng.capture(max_steps, tick_fn)
-                graph.replay()
-            else:
-                for _ in range(max_steps):
-                    tick_fn()
-            epsilon = max(min_epsilon, initial_epsilon * np.exp(-epsilon_decay * episode))
-            average_loss = float(self._acc_loss.item()) / max_steps
-            ep_reward = float(self._acc_reward.item())
-            # the per-tick scalars of the episode, read once (train_gcn_dqn.py:136,174)
-            rew_t, loss_t, tr_t = self._tick_reward.tolist(), self._tick_loss.tolist(), self._tick_trained.tolist()
-            for i in range(max_steps):
-                ticks += 1
-                self.writer.add_scalar("Reward", rew_t[i], ticks)
-                if tr_t[i]:
-                    self.writer.add_scalar("Loss", loss_t[i], ticks)
-            eng.check_handoffs()   # an overrun hand-off dropped TD graphs: fail loudly (one 4-byte read)
-            if eng.peer is not None:
-                eng.peer.check()   # an expired peer-exchange wait: the summed gradient is wrong
-            self.episode_losses.append(average_loss)
-            self.rewards_buffer.append(torch.tensor(ep_reward))
-            if (episode + 1) % 10 == 0:
-                self.episode_rewards.append(sum(self.rewards_buffer) / 10)
-                self.rewards_buffer = []
-            print(f"Episode {episode}, Loss: {average_loss}, Reward: {ep_reward * self.env.n_agents}, "
-                  f"Epsilon: {epsilon}")
-        print("Training completed")
-        self._sync_models()
-        os.makedirs(self.models_path, exist_ok=True)
-        torch.save(self.model.state_dict(), f"{self.models_path}/experiment_{self.experiment}-seed_{self.seed}.pth")
-        print("Model saved successfully!")
-        self.save_metrics_to_csv()
+        _train_loop(self, self.engine, [self], (), config, "", "Model saved successfully!")
 
     def save_metrics_to_csv(self):
         os.makedirs(self.stats_path, exist_ok=True)
@@ -275,62 +228,76 @@ class PopulationTrainer:
             self._tick_trained[i].copy_(pop.ctrl[:, 7])
         return tick
 
+    def _check_episode(self):
+        self.population.check_handoffs()
+
     def train_model(self, config):
-        pop, trainers = self.population, self.trainers
-        P, dev = pop.P, pop.device
-        initial_epsilon = config["epsilon"]
-        epsilon_decay = config["epsilon_decay"]
-        min_epsilon = config["min_epsilon"]
-        episodes = config["episodes"]
-        max_steps = trainers[0].env.max_steps or 100
-        epsilon = initial_epsilon
-        self._acc_reward = torch.zeros(P, device=dev)
-        self._acc_loss = torch.zeros(P, device=dev)
-        self._tick_reward = torch.zeros(max_steps, P, device=dev)
-        self._tick_loss = torch.zeros(max_steps, P, device=dev)
-        self._tick_trained = torch.zeros(max_steps, P, dtype=torch.int32, device=dev)
-        tick_fn = self._episode_fn(max_steps)
-        ticks = 0
-        graph = None
-        for episode in range(episodes):
-            pop.reset()
-            pop.set_eps(epsilon)
-            self._acc_reward.zero_()
-            self._acc_loss.zero_()
-            if trainers[0].use_graph and episode > 0:
-                if graph is None:   # episode 0 ran eagerly (warm-up); capture one whole episode once
-                    graph = pop.capture(max_steps, tick_fn)
-                graph.replay()
-            else:
-                for _ in range(max_steps):
-                    tick_fn()
-            epsilon = max(min_epsilon, initial_epsilon * np.exp(-epsilon_decay * episode))
-            # the episode's scalars of every member, read once
-            acc_loss, acc_reward = self._acc_loss.tolist(), self._acc_reward.tolist()
-            rew_t, loss_t, tr_t = self._tick_reward.tolist(), self._tick_loss.tolist(), self._tick_trained.tolist()
-            pop.check_handoffs()
-            for m, t in enumerate(trainers):
-                average_loss = acc_loss[m] / max_steps
-                ep_reward = acc_reward[m]
-                for i in range(max_steps):
-                    t.writer.add_scalar("Reward", rew_t[i][m], ticks + i + 1)
-                    if tr_t[i][m]:
-                        t.writer.add_scalar("Loss", loss_t[i][m], ticks + i + 1)
-                t.episode_losses.append(average_loss)
-                t.rewards_buffer.append(torch.tensor(ep_reward))
-                if (episode + 1) % 10 == 0:
-                    t.episode_rewards.append(sum(t.rewards_buffer) / 10)
-                    t.rewards_buffer = []
-                print(f"Seed {t.seed}, Episode {episode}, Loss: {average_loss}, Reward: {ep_reward * t.env.n_agents}, "
-                      f"Epsilon: {epsilon}")
-            ticks += max_steps
-        print("Training completed")
-        for t in trainers:
-            t._sync_models()
-            os.makedirs(t.models_path, exist_ok=True)
-            torch.save(t.model.state_dict(), f"{t.models_path}/experiment_{t.experiment}-seed_{t.seed}.pth")
-            t.save_metrics_to_csv()
-        print("Models saved successfully!")
+        _train_loop(self, self.population, self.trainers, (self.population.P,), config, "Seed {seed}, ",
+                    "Models saved successfully!")
+
+
+def _train_loop(driver, group, trainers, shape, config, prefix: str, saved: str):
+    """The reference's episode loop (train_gcn_dqn.py:139-204) for ``trainers`` ticked together by
+    ``group`` (a SwarmEngine with its one trainer, or a SwarmPopulation): reset / set_eps / capture.
+    ``driver`` owns what differs between the two: the tick with its device-side bookkeeping
+    (``_episode_fn``, on per-episode buffers of ``shape``, per-tick ones of [max_steps, *shape]: () for
+    a lone engine, (P,) for a population) and the end-of-episode checks (``_check_episode``)."""
+    first, P = trainers[0], len(trainers)
+    initial_epsilon = config["epsilon"]
+    epsilon_decay = config["epsilon_decay"]
+    min_epsilon = config["min_epsilon"]
+    episodes = config["episodes"]
+    max_steps = first.env.max_steps or 100
+    epsilon = initial_epsilon
+    driver._acc_reward = torch.zeros(shape, device=group.device)
+    driver._acc_loss = torch.zeros(shape, device=group.device)
+    driver._tick_reward = torch.zeros((max_steps, *shape), device=group.device)
+    driver._tick_loss = torch.zeros((max_steps, *shape), device=group.device)
+    driver._tick_trained = torch.zeros((max_steps, *shape), dtype=torch.int32, device=group.device)
+    tick_fn = driver._episode_fn(max_steps)
+    ticks = 0
+    graph = None
+    for episode in range(episodes):
+        group.reset()
+        group.set_eps(epsilon)
+        driver._acc_reward.zero_()
+        driver._acc_loss.zero_()
+        if first.use_graph and episode > 0:
+            if graph is None:   # episode 0 ran eagerly (warm-up); capture one whole episode once
+                graph = group.capture(max_steps, tick_fn)
+            graph.replay()
+        else:
+            for _ in range(max_steps):
+                tick_fn()
+        epsilon = max(min_epsilon, initial_epsilon * np.exp(-epsilon_decay * episode))
+        # the episode's scalars of every member, read once: the sums [P], the per-tick ones [max_steps][P]
+        acc_loss, acc_reward = driver._acc_loss.reshape(P).tolist(), driver._acc_reward.reshape(P).tolist()
+        rew_t, loss_t, tr_t = (x.reshape(max_steps, P).tolist()
+                               for x in (driver._tick_reward, driver._tick_loss, driver._tick_trained))
+        driver._check_episode()
+        for m, t in enumerate(trainers):
+            average_loss = acc_loss[m] / max_steps
+            ep_reward = acc_reward[m]
+            # the per-tick scalars of the episode (train_gcn_dqn.py:136,174)
+            for i in range(max_steps):
+                t.writer.add_scalar("Reward", rew_t[i][m], ticks + i + 1)
+                if tr_t[i][m]:
+                    t.writer.add_scalar("Loss", loss_t[i][m], ticks + i + 1)
+            t.episode_losses.append(average_loss)
+            t.rewards_buffer.append(torch.tensor(ep_reward))
+            if (episode + 1) % 10 == 0:
+                t.episode_rewards.append(sum(t.rewards_buffer) / 10)
+                t.rewards_buffer = []
+            print(f"{prefix.format(seed=t.seed)}Episode {episode}, Loss: {average_loss}, "
+                  f"Reward: {ep_reward * t.env.n_agents}, Epsilon: {epsilon}")
+        ticks += max_steps
+    print("Training completed")
+    for t in trainers:
+        t._sync_models()
+        os.makedirs(t.models_path, exist_ok=True)
+        torch.save(t.model.state_dict(), f"{t.models_path}/experiment_{t.experiment}-seed_{t.seed}.pth")
+        t.save_metrics_to_csv()
+    print(saved)
 
 
 class SimpleAdamView:

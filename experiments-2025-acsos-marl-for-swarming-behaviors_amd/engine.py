@@ -39,8 +39,7 @@ import torch
 
 from . import _lib
 from .dist import allreduce_grad_
-from ._lib import (CTRL, N_PARAMS, SwarmActOut, SwarmAdamCfg, SwarmConfig, SwarmLearner, SwarmReplay, check, ptr,
-                   stream_ptr)
+from ._lib import CTRL, N_PARAMS, SwarmActOut, SwarmAdamCfg, SwarmConfig, SwarmLearner, SwarmReplay, call, ptr
 
 SCENARIOS = {"GoTo": _lib.SWARM_GOTO, "ObstacleAvoidance": _lib.SWARM_OBSTACLE_AVOIDANCE,
              "Flocking": _lib.SWARM_FLOCKING, "go_to": _lib.SWARM_GOTO,
@@ -139,8 +138,7 @@ class SwarmEngine:
         f32 = dict(dtype=torch.float32, device=dev)
         # [B][N][4] pos.xy, vel.xy; Flocking keeps its per-agent previous_distance_to_agents after
         # it (swarm_state_floats), as `scenario_state` [B][N]
-        nst = int(self.lib.swarm_state_floats(ctypes_ref(self.cfg)))
-        check(min(nst, 0), "swarm_state_floats")
+        nst = _lib.size(self.lib, "swarm_state_floats", self.cfg)
         self._state_buf = torch.zeros(max(nst, 1), **f32)
         self.state = self._state_buf[: n_envs * n_agents * 4].view(n_envs, n_agents, 4)
         self.scenario_state = (self._state_buf[n_envs * n_agents * 4: nst].view(n_envs, n_agents)
@@ -164,8 +162,7 @@ class SwarmEngine:
         self.params.copy_(p0)
         self.target.copy_(p0)
         self.ctrl = torch.zeros(_lib.CTRL_WORDS, dtype=torch.int32, device=dev)
-        check(self.lib.swarm_ctrl_init(ctypes_ref(self.hp), float(eps), ptr(self.ctrl), stream_ptr()),
-              "swarm_ctrl_init")
+        call(self.lib, "swarm_ctrl_init", self.hp, float(eps), ptr(self.ctrl))
         self.episode = 0
         cap = max(1, -(-replay_capacity // n_envs)) if learn else 1
         self.capacity = cap
@@ -174,11 +171,9 @@ class SwarmEngine:
         self.rep_r = torch.zeros(cap, n_envs, n_agents, **f32)
         self.rep_a = torch.zeros(cap, n_envs, n_agents, dtype=torch.uint8, device=dev)
         self.replay = SwarmReplay(ptr(self.rep_s), ptr(self.rep_s1), ptr(self.rep_r), ptr(self.rep_a), cap, 0)
-        ws = self.lib.swarm_td_workspace_floats(ctypes_ref(self.cfg), self.batch) if net == "gcn" else 4
-        if ws < 0:
-            check(int(ws), "swarm_td_workspace_floats")
-        self.fused = learn and bool(self.lib.swarm_train_tick_supported(ctypes_ref(self.cfg)))
-        self.slabs = torch.zeros(int(ws), **f32)
+        ws = _lib.size(self.lib, "swarm_td_workspace_floats", self.cfg, self.batch) if net == "gcn" else 4
+        self.fused = learn and bool(self.lib.swarm_train_tick_supported(_lib.ref(self.cfg)))
+        self.slabs = torch.zeros(ws, **f32)
         # + the reduce's norm partials (ABI 10); a write to grad from outside the library's reduce
         # must be declared with grad_written() (the partials then no longer describe it)
         self.grad = torch.zeros(_lib.GRAD_FLOATS, **f32)
@@ -188,9 +183,8 @@ class SwarmEngine:
         # fused-tick workspace (error word, launch counters, hand-off granule records); zeroed with ctrl
         self.tick_ws = None
         if self.fused:
-            nb = self.lib.swarm_train_tick_workspace_bytes(ctypes_ref(self.cfg))
-            check(int(min(nb, 0)), "swarm_train_tick_workspace_bytes")
-            self.tick_ws = torch.zeros(int(nb), dtype=torch.uint8, device=dev)
+            nb = _lib.size(self.lib, "swarm_train_tick_workspace_bytes", self.cfg)
+            self.tick_ws = torch.zeros(nb, dtype=torch.uint8, device=dev)
         # per-tick outputs
         self.q = torch.zeros(n_envs, n_agents, 9, **f32)
         self.actions = torch.zeros(n_envs, n_agents, dtype=torch.int32, device=dev)
@@ -198,6 +192,11 @@ class SwarmEngine:
         self.obs = torch.zeros(n_envs, n_agents, 6, **f32)
         self.avg_dist = torch.zeros(n_envs, **f32)
         self.hits = torch.zeros(n_envs, **f32)
+        self.bind_outputs()
+
+    def bind_outputs(self):
+        """``out`` / ``out_min`` (the full and the trainer's output set) from the tensors the
+        engine holds now; a population calls it again after it re-homed some of them."""
         self.out = SwarmActOut(ptr(self.q), ptr(self.actions), ptr(self.reward), ptr(self.obs),
                                ptr(self.avg_dist), ptr(self.hits), 0, 0, 0, 0)
         self.out_min = SwarmActOut(0, 0, ptr(self.reward), 0, ptr(self.avg_dist), ptr(self.hits), 0, 0, 0, 0)
@@ -207,10 +206,7 @@ class SwarmEngine:
         self.ctrl.view(torch.float32)[CTRL["eps"]].fill_(float(eps))
 
     def read_ctrl(self) -> dict:
-        c = self.ctrl.cpu()
-        f = c.view(torch.float32)
-        return dict(tick=int(c[0]), write_slot=int(c[1]), filled_slots=int(c[2]), adam_step=int(c[3]),
-                    eps=float(f[4]), loss=float(f[5]), grad_norm=float(f[6]), trained=int(c[7]))
+        return decode_ctrl(self.ctrl.cpu())
 
     def replay_len(self) -> int:
         """len(GraphReplayBuffer) in graphs (one graph = one env transition)."""
@@ -219,7 +215,7 @@ class SwarmEngine:
     # ------------------------------------------------------------------ env
     def reset(self, episode: Optional[int] = None):
         ep = self.episode if episode is None else episode
-        check(self.lib.swarm_env_reset(ctypes_ref(self.cfg), ptr(self.state), ep, stream_ptr()), "swarm_env_reset")
+        call(self.lib, "swarm_env_reset", self.cfg, ptr(self.state), ep)
         self.episode = ep + 1
         return self.state
 
@@ -227,24 +223,19 @@ class SwarmEngine:
         """Write agent positions/velocities [B, N, 2] and bring the scenario's per-agent state in
         line with them (Flocking): fresh=True as right after reset_world_at, else as after a step."""
         self.state.copy_(torch.cat([pos, vel], -1).to(self.state))
-        check(self.lib.swarm_env_sync_state(ctypes_ref(self.cfg), ptr(self.state), int(fresh), stream_ptr()),
-              "swarm_env_sync_state")
+        call(self.lib, "swarm_env_sync_state", self.cfg, ptr(self.state), int(fresh))
 
     def env_step(self, actions: torch.Tensor, out: Optional[SwarmActOut] = None):
         a = actions.to(device=self.device, dtype=torch.int32).contiguous()
-        check(self.lib.swarm_env_step(ctypes_ref(self.cfg), ptr(self.state), ptr(a),
-                                      ctypes_ref(out or self.out), stream_ptr()), "swarm_env_step")
+        call(self.lib, "swarm_env_step", self.cfg, ptr(self.state), ptr(a), out or self.out)
 
     # ------------------------------------------------------------------ acting
     def act(self, push: bool = True, full_out: bool = True):
-        check(self.lib.swarm_act_step(ctypes_ref(self.cfg), ptr(self.params), ptr(self.state),
-                                      ctypes_ref(self.replay) if push else None, ptr(self.ctrl),
-                                      ctypes_ref(self.out if full_out else self.out_min), stream_ptr()),
-              "swarm_act_step")
+        call(self.lib, "swarm_act_step", self.cfg, ptr(self.params), ptr(self.state),
+             self.replay if push else None, ptr(self.ctrl), self.out if full_out else self.out_min)
 
     def advance(self):
-        check(self.lib.swarm_ctrl_advance(ctypes_ref(self.cfg), ctypes_ref(self.replay), ptr(self.ctrl),
-                                          stream_ptr()), "swarm_ctrl_advance")
+        call(self.lib, "swarm_ctrl_advance", self.cfg, self.replay, ptr(self.ctrl))
 
     def rollout(self, n_ticks: int, tick0: int = 0, eps: float = 0.0, traj: bool = False, params=None):
         """Acting-only rollout in one launch; tick t is keyed tick0 + t.  Returns ``reward`` [B, N],
@@ -261,18 +252,17 @@ class SwarmEngine:
         out = SwarmActOut(0, 0, ptr(res["reward"]), ptr(res["obs"]), ptr(res["avg_dist"]), ptr(res["hits"]), 0,
                           ptr(res.get("traj_pos")), ptr(res.get("traj_dist")), ptr(res.get("traj_hits")))
         p = self.params if params is None else params
-        check(self.lib.swarm_rollout(ctypes_ref(self.cfg), ptr(p), ptr(self.state), n_ticks, tick0, eps,
-                                     ctypes_ref(out), stream_ptr()), "swarm_rollout")
+        call(self.lib, "swarm_rollout", self.cfg, ptr(p), ptr(self.state), n_ticks, tick0, eps, out)
         return res
 
     # ------------------------------------------------------------------ learning
+    def _td(self, params, sample_in, sample_out):
+        call(self.lib, "swarm_td_grad", self.cfg, self.hp, ptr(params), ptr(self.target), self.replay,
+             ptr(self.ctrl), ptr(sample_in), ptr(sample_out), ptr(self.slabs))
+
     def td_grad(self, sample_in: Optional[torch.Tensor] = None, sample_out: Optional[torch.Tensor] = None):
-        check(self.lib.swarm_td_grad(ctypes_ref(self.cfg), ctypes_ref(self.hp), ptr(self.params), ptr(self.target),
-                                     ctypes_ref(self.replay), ptr(self.ctrl), ptr(sample_in), ptr(sample_out),
-                                     ptr(self.slabs), stream_ptr()), "swarm_td_grad")
-        self._grad_dirty = False
-        check(self.lib.swarm_grad_reduce(ctypes_ref(self.cfg), ctypes_ref(self.hp), ptr(self.slabs),
-                                         ptr(self.grad), stream_ptr()), "swarm_grad_reduce")
+        self._td(self.params, sample_in, sample_out)
+        self.launch_grad_reduce()
 
     def _sync_flags(self):
         """swarm_adam_cfg.flags for the next launches: the reduce's clip-norm partials describe
@@ -281,7 +271,7 @@ class SwarmEngine:
         write declared with ``grad_written()``.  Otherwise the optimizer prologue forms
         the norm from the gradient itself (the same summation order, so both give the same bits)."""
         exact = (self.world_size == 1 or self.peer is not None) and not self._grad_dirty
-        self.hp.flags = _lib.ADAM_F_NORM_PARTIALS if exact else 0
+        self.hp.flags = norm_flags(exact)
 
     def grad_written(self):
         """Declare a write to ``grad`` made outside the library's reduce (e.g. a hand-made
@@ -295,14 +285,12 @@ class SwarmEngine:
         allreduce_grad_(g, self.world_size, self.process_group, self.peer)
 
     def adam(self):
-        check(self.lib.swarm_adam_step(ctypes_ref(self.cfg), ctypes_ref(self.hp), ptr(self.params), ptr(self.target),
-                                       ptr(self.adam_m), ptr(self.adam_v), ptr(self.grad), self.capacity,
-                                       ptr(self.ctrl), stream_ptr()), "swarm_adam_step")
+        call(self.lib, "swarm_adam_step", self.cfg, self.hp, ptr(self.params), ptr(self.target), ptr(self.adam_m),
+             ptr(self.adam_v), ptr(self.grad), self.capacity, ptr(self.ctrl))
 
     def flush(self):
         """Apply a pending fused optimizer step to the current weights (no-op if none)."""
-        check(self.lib.swarm_adam_flush(ctypes_ref(self.cfg), ctypes_ref(self.hp), ctypes_ref(self.learner),
-                                        ptr(self.ctrl), stream_ptr()), "swarm_adam_flush")
+        call(self.lib, "swarm_adam_flush", self.cfg, self.hp, self.learner, ptr(self.ctrl))
 
     def td_update(self, sample_in=None, sample_out=None):
         """Unfused TD update (API path): applies the optimizer step immediately."""
@@ -316,44 +304,34 @@ class SwarmEngine:
         self.td_update()
 
     # single launches of the fused tick (bench.py times each kernel as a back-to-back chain)
-    def launch_train_act(self):
+    def launch_train_act(self, full_out: bool = False):
         self._sync_flags()
-        check(self.lib.swarm_train_act_step(ctypes_ref(self.cfg), ctypes_ref(self.hp), ctypes_ref(self.learner),
-                                            ptr(self.state), ctypes_ref(self.replay), ptr(self.ctrl),
-                                            ctypes_ref(self.out_min), ptr(self.samples), stream_ptr()),
-              "swarm_train_act_step")
+        call(self.lib, "swarm_train_act_step", self.cfg, self.hp, self.learner, ptr(self.state), self.replay,
+             ptr(self.ctrl), self.out if full_out else self.out_min, ptr(self.samples))
 
     def launch_td(self):
-        check(self.lib.swarm_td_grad(ctypes_ref(self.cfg), ctypes_ref(self.hp), ptr(self.w_nxt), ptr(self.target),
-                                     ctypes_ref(self.replay), ptr(self.ctrl), ptr(self.samples), None,
-                                     ptr(self.slabs), stream_ptr()), "swarm_td_grad")
+        self._td(self.w_nxt, self.samples, None)
 
     def launch_grad_reduce(self):
         self._grad_dirty = False
-        check(self.lib.swarm_grad_reduce(ctypes_ref(self.cfg), ctypes_ref(self.hp), ptr(self.slabs),
-                                         ptr(self.grad), stream_ptr()), "swarm_grad_reduce")
+        call(self.lib, "swarm_grad_reduce", self.cfg, self.hp, ptr(self.slabs), ptr(self.grad))
 
     def launch_tick(self, full_out: bool = False):
         """The fused tick's launch (acting + TD blocks); swarm_reduce_advance follows it."""
         self._sync_flags()
-        check(self.lib.swarm_train_tick(ctypes_ref(self.cfg), ctypes_ref(self.hp), ctypes_ref(self.learner),
-                                        ptr(self.state), ctypes_ref(self.replay), ptr(self.ctrl),
-                                        ctypes_ref(self.out if full_out else self.out_min), ptr(self.slabs),
-                                        ptr(self.tick_ws), ptr(self.samples), stream_ptr()), "swarm_train_tick")
+        call(self.lib, "swarm_train_tick", self.cfg, self.hp, self.learner, ptr(self.state), self.replay,
+             ptr(self.ctrl), self.out if full_out else self.out_min, ptr(self.slabs), ptr(self.tick_ws),
+             ptr(self.samples))
 
     def launch_reduce_advance(self):
         """Slab reduce + ctrl advance; with a peer exchange, the gradient all-reduce too."""
         self._grad_dirty = False
+        peer = ()
         if self.peer is not None:
             self.peer.check_stream()
-            check(self.lib.swarm_reduce_advance_peer(ctypes_ref(self.cfg), ctypes_ref(self.hp), ptr(self.slabs),
-                                                     ctypes_ref(self.learner), self.capacity, ptr(self.ctrl),
-                                                     ctypes_ref(self.peer.struct), stream_ptr()),
-                  "swarm_reduce_advance_peer")
-            return
-        check(self.lib.swarm_reduce_advance(ctypes_ref(self.cfg), ctypes_ref(self.hp), ptr(self.slabs),
-                                            ctypes_ref(self.learner), self.capacity, ptr(self.ctrl), stream_ptr()),
-              "swarm_reduce_advance")
+            peer = (self.peer.struct,)
+        call(self.lib, "swarm_reduce_advance_peer" if peer else "swarm_reduce_advance", self.cfg, self.hp,
+             ptr(self.slabs), self.learner, self.capacity, ptr(self.ctrl), *peer)
 
     def handoff_errors(self) -> int:
         """Hand-off waits of the fused tick that hit their bound (0 in a correct run)."""
@@ -384,15 +362,8 @@ class SwarmEngine:
 
     def train_tick3(self, full_out: bool = False):
         """3-launch training tick: act (+ this tick's TD batch indices), TD, reduce."""
-        self._sync_flags()
-        cfg, hp = ctypes_ref(self.cfg), ctypes_ref(self.hp)
-        check(self.lib.swarm_train_act_step(cfg, hp, ctypes_ref(self.learner), ptr(self.state),
-                                            ctypes_ref(self.replay), ptr(self.ctrl),
-                                            ctypes_ref(self.out if full_out else self.out_min), ptr(self.samples),
-                                            stream_ptr()), "swarm_train_act_step")
-        check(self.lib.swarm_td_grad(cfg, hp, ptr(self.w_nxt), ptr(self.target), ctypes_ref(self.replay),
-                                     ptr(self.ctrl), ptr(self.samples), None, ptr(self.slabs), stream_ptr()),
-              "swarm_td_grad")
+        self.launch_train_act(full_out)
+        self.launch_td()
         self.launch_reduce_advance()
         if self.peer is None:
             self.allreduce_grad()
@@ -402,17 +373,8 @@ class SwarmEngine:
         """Capture n_ticks calls of ``fn`` (default train_tick) into one hipGraph.  With
         world_size > 1 the tick's RCCL all-reduce is captured too; the capture is then
         thread-local so the process group's watchdog thread may keep querying its events."""
-        fn = fn or self.train_tick
-        s = torch.cuda.Stream(device=self.device)
-        s.wait_stream(torch.cuda.current_stream())
-        graph = torch.cuda.CUDAGraph()
-        mode = "thread_local" if self.world_size > 1 else "global"
-        with torch.cuda.stream(s):
-            with torch.cuda.graph(graph, stream=s, capture_error_mode=mode):
-                for _ in range(n_ticks):
-                    fn()
-        torch.cuda.current_stream().wait_stream(s)
-        return graph
+        return capture_ticks(self.device, n_ticks, fn or self.train_tick,
+                             "thread_local" if self.world_size > 1 else "global")
 
     # ------------------------------------------------------------------ weights
     def state_dict(self) -> dict:
@@ -425,6 +387,27 @@ class SwarmEngine:
         self.target.copy_(self.params)
 
 
-def ctypes_ref(obj):
-    import ctypes
-    return None if obj is None else ctypes.byref(obj)
+def norm_flags(exact: bool) -> int:
+    """swarm_adam_cfg.flags: the reduce's clip-norm partials stand for the gradient's norm only
+    while they are exact, i.e. nothing but the library's reduce has written the gradient."""
+    return _lib.ADAM_F_NORM_PARTIALS if exact else 0
+
+
+def decode_ctrl(row: torch.Tensor) -> dict:
+    """What ``read_ctrl`` reports of one control block (a host int32 tensor of CTRL_WORDS words)."""
+    f = row.view(torch.float32)
+    return {k: (float(f[CTRL[k]]) if k in ("eps", "loss", "grad_norm") else int(row[CTRL[k]]))
+            for k in ("tick", "write_slot", "filled_slots", "adam_step", "eps", "loss", "grad_norm", "trained")}
+
+
+def capture_ticks(device, n_ticks: int, fn, mode: str = "global"):
+    """n_ticks calls of ``fn`` captured into one hipGraph on a side stream."""
+    s = torch.cuda.Stream(device=device)
+    s.wait_stream(torch.cuda.current_stream())
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.stream(s):
+        with torch.cuda.graph(graph, stream=s, capture_error_mode=mode):
+            for _ in range(n_ticks):
+                fn()
+    torch.cuda.current_stream().wait_stream(s)
+    return graph

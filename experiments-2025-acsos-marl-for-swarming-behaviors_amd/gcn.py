@@ -28,9 +28,9 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._lib import check, ptr, stream_ptr
+from ._lib import call, ptr
 from .engine import param_order
-from .graph import Data, _lib_byref, _round4, edges_to_mult, q_backward
+from .graph import Data, _round4, edges_to_mult, q_backward
 
 
 class GATConvParams(nn.Module):
@@ -120,8 +120,7 @@ class GCN(nn.Module):
 
     def _q_forward(self, params, x, cfg, mult) -> torch.Tensor:
         q = torch.empty(x.shape[0], 9, dtype=torch.float32, device=x.device)
-        check(_lib.load().swarm_q_forward(_lib_byref(cfg), ptr(params), ptr(x), ptr(mult), ptr(q), stream_ptr()),
-              "swarm_q_forward")
+        call(_lib.load(), "swarm_q_forward", cfg, ptr(params), ptr(x), ptr(mult), ptr(q))
         return q
 
     def forward(self, data: Data) -> torch.Tensor:

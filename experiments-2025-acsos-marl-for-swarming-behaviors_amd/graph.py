@@ -24,7 +24,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import check, ptr, stream_ptr
+from ._lib import call, ptr
 
 
 class Data:
@@ -128,7 +128,7 @@ def build_mult(data: Data) -> torch.Tensor:
         m = data.swarm
         mult = torch.zeros(_round4(m["n_graphs"] * m["n_nodes"] ** 2), dtype=torch.uint8, device=x.device)
         cfg = graph_config(data)
-        check(lib.swarm_build_graph(_lib_byref(cfg), ptr(x), ptr(mult), stream_ptr()), "swarm_build_graph")
+        call(lib, "swarm_build_graph", cfg, ptr(x), ptr(mult))
         return mult[: m["n_graphs"] * m["n_nodes"] ** 2].view(m["n_graphs"], m["n_nodes"], m["n_nodes"])
     G = data.num_graphs
     N = data.num_nodes // G
@@ -140,8 +140,7 @@ def edges_to_mult(edge_index: torch.Tensor, n_graphs: int, n_nodes: int) -> torc
     ei = edge_index.to("cuda", torch.int64).contiguous()
     mult = torch.zeros(_round4(n_graphs * n_nodes * n_nodes), dtype=torch.uint8, device=ei.device)
     err = torch.zeros(1, dtype=torch.int32, device=ei.device)
-    check(lib.swarm_edges_to_mult(ptr(ei), ei.shape[1], n_graphs, n_nodes, ptr(mult), ptr(err), stream_ptr()),
-          "swarm_edges_to_mult")
+    call(lib, "swarm_edges_to_mult", ptr(ei), ei.shape[1], n_graphs, n_nodes, ptr(mult), ptr(err))
     if int(err.item()) != 0:
         raise ValueError("edge_index has an edge between different graphs (expected Batch of equal-size graphs)")
     return mult[: n_graphs * n_nodes * n_nodes].view(n_graphs, n_nodes, n_nodes)
@@ -154,13 +153,10 @@ def q_backward(params: torch.Tensor, x: torch.Tensor, cfg: "_lib.SwarmConfig", m
     (``mult``: the dense multiplicities, or None).  Returns [N_PARAMS] float32 on the GPU."""
     lib = _lib.load()
     dq = dq.to(x.device, torch.float32).contiguous()
-    n_ws = lib.swarm_td_workspace_floats(_lib_byref(cfg), cfg.n_envs)
-    if n_ws < 0:
-        check(int(n_ws), "swarm_td_workspace_floats")
+    n_ws = _lib.size(lib, "swarm_td_workspace_floats", cfg, cfg.n_envs)
     ws = torch.empty(n_ws, dtype=torch.float32, device=x.device)
     grad = torch.empty(_lib.GRAD_FLOATS, dtype=torch.float32, device=x.device)
-    check(lib.swarm_q_backward(_lib_byref(cfg), ptr(params), ptr(x), ptr(mult), ptr(dq), ptr(ws), ptr(grad),
-                               stream_ptr()), "swarm_q_backward")
+    call(lib, "swarm_q_backward", cfg, ptr(params), ptr(x), ptr(mult), ptr(dq), ptr(ws), ptr(grad))
     return grad[: _lib.N_PARAMS]
 
 
@@ -177,8 +173,3 @@ def edge_index_from_mult(mult: torch.Tensor) -> torch.Tensor:
 
 def _round4(n: int) -> int:
     return (n + 3) & ~3
-
-
-def _lib_byref(obj):
-    import ctypes
-    return ctypes.byref(obj)

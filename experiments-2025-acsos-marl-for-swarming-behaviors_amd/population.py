@@ -24,9 +24,8 @@ from typing import Sequence
 
 import torch
 
-from . import _lib
-from ._lib import CTRL, SwarmActOut, SwarmAdamCfg, SwarmConfig, SwarmPopMember, check, ptr, stream_ptr
-from .engine import SwarmEngine, ctypes_ref
+from ._lib import CTRL, SwarmAdamCfg, SwarmConfig, SwarmPopMember, call, ptr
+from .engine import SwarmEngine, capture_ticks, decode_ctrl, norm_flags
 
 
 def _bytes_of(struct) -> bytes:
@@ -103,9 +102,7 @@ class SwarmPopulation:
             self.tick_ws[m, :nb].copy_(e.tick_ws)
             e.ctrl, e.reward, e.avg_dist, e.hits = self.ctrl[m], self.reward[m], self.avg_dist[m], self.hits[m]
             e.tick_ws = self.tick_ws[m, :nb]
-            e.out = SwarmActOut(ptr(e.q), ptr(e.actions), ptr(e.reward), ptr(e.obs), ptr(e.avg_dist), ptr(e.hits),
-                                0, 0, 0, 0)
-            e.out_min = SwarmActOut(0, 0, ptr(e.reward), 0, ptr(e.avg_dist), ptr(e.hits), 0, 0, 0, 0)
+            e.bind_outputs()
         # the descriptor tables in device memory, written once: one per output set of train_tick
         self._table_full = self._table(lambda e: e.out)
         self._table_min = self._table(lambda e: e.out_min)
@@ -124,15 +121,13 @@ class SwarmPopulation:
         go to its ``samples``; with full_out its Q, actions and obs are written too."""
         # the reduce's clip-norm partials describe every member's grad unless one declared a write
         dirty = any(e._grad_dirty for e in self.members)
-        self.hp.flags = 0 if dirty else _lib.ADAM_F_NORM_PARTIALS
+        self.hp.flags = norm_flags(not dirty)
         table = self._table_full if full_out else self._table_min
-        cfg, hp = ctypes_ref(self.cfg), ctypes_ref(self.hp)
-        check(self.lib.swarm_pop_train_tick(cfg, hp, ptr(table), self.P, stream_ptr()), "swarm_pop_train_tick")
+        call(self.lib, "swarm_pop_train_tick", self.cfg, self.hp, ptr(table), self.P)
         if dirty:
             for e in self.members:
                 e._grad_dirty = False   # the reduce below rewrites grad and its partials
-        check(self.lib.swarm_pop_reduce_advance(cfg, hp, ptr(table), self.P, stream_ptr()),
-              "swarm_pop_reduce_advance")
+        call(self.lib, "swarm_pop_reduce_advance", self.cfg, self.hp, ptr(table), self.P)
 
     def reset(self, episode=None):
         """Reset every member's environments (one small launch per member, once per episode)."""
@@ -157,16 +152,7 @@ class SwarmPopulation:
 
     def capture(self, n_ticks: int, fn=None):
         """Capture n_ticks calls of ``fn`` (default train_tick) into one hipGraph, on one stream."""
-        fn = fn or self.train_tick
-        s = torch.cuda.Stream(device=self.device)
-        s.wait_stream(torch.cuda.current_stream())
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.stream(s):
-            with torch.cuda.graph(graph, stream=s):
-                for _ in range(n_ticks):
-                    fn()
-        torch.cuda.current_stream().wait_stream(s)
-        return graph
+        return capture_ticks(self.device, n_ticks, fn or self.train_tick)
 
     # ------------------------------------------------------------------ reading back
     def handoff_errors(self) -> list:
@@ -184,7 +170,4 @@ class SwarmPopulation:
     def read_ctrl(self) -> list:
         """Every member's control block as SwarmEngine.read_ctrl gives it; one device read."""
         c = self.ctrl.cpu()
-        f = c.view(torch.float32)
-        return [dict(tick=int(c[m, 0]), write_slot=int(c[m, 1]), filled_slots=int(c[m, 2]), adam_step=int(c[m, 3]),
-                     eps=float(f[m, 4]), loss=float(f[m, 5]), grad_norm=float(f[m, 6]), trained=int(c[m, 7]))
-                for m in range(self.P)]
+        return [decode_ctrl(c[m]) for m in range(self.P)]

@@ -142,6 +142,24 @@ def test_host_topk_matches_torch_fixture():
                                    4, 5, sel) == -2
 
 
+def test_call_helper_names_the_entry_point_and_passes_none_as_null():
+    """_lib.call: a status the library returns before any launch (k > n) raises a RuntimeError
+    that names the entry point and the status; a None structure argument arrives as NULL."""
+    L, lib = _host_lib()
+    sel = (ctypes.c_uint8 * 32)()
+    d = np.zeros(4, np.float32).ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+    with pytest.raises(RuntimeError) as e:
+        L.call(lib, "swarm_host_topk_set", d, 4, 5, sel)
+    assert "swarm_host_topk_set" in str(e.value) and "SWARM_E_KNN_K" in str(e.value)
+    assert L.call(lib, "swarm_host_topk_set", d, 4, 4, sel) is None and list(sel[:4]) == [1, 1, 1, 1]
+    assert lib.swarm_train_tick_supported(L.ref(None)) == 0
+    cfg = L.SwarmConfig(1, 5, L.SWARM_GOTO, L.GRAPH_COMPLETE, 0, L.CONV_GAT, 0, 0, 0, 0.3, L.NET_GCN)
+    assert lib.swarm_train_tick_supported(L.ref(cfg)) == 1
+    with pytest.raises(RuntimeError, match="swarm_train_tick_workspace_bytes failed: SWARM_E_UNSUPPORTED"):
+        L.size(lib, "swarm_train_tick_workspace_bytes", None)
+    assert L.size(lib, "swarm_train_tick_workspace_bytes", cfg) > 512
+
+
 def test_host_topk_random_ties_vs_torch():
     L, lib = _host_lib()
     rng = np.random.default_rng(7)

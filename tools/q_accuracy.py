@@ -17,7 +17,6 @@ import torch  # noqa: E402
 
 import swarm_amd  # noqa: E402
 from swarm_amd import _lib  # noqa: E402
-from swarm_amd.engine import ctypes_ref  # noqa: E402
 from oracle import swarm_oracle as O  # noqa: E402
 
 
@@ -53,8 +52,7 @@ def main():
                 q64 = O.gcn_conv_dense({k: v.double() for k, v in params.items()}, x.double(), mult.double())
             qg = torch.zeros(512 * N, 9, device="cuda")
             xg = x.reshape(-1, 7).contiguous().cuda()
-            _lib.check(eng.lib.swarm_q_forward(ctypes_ref(eng.cfg), eng.params.data_ptr(), xg.data_ptr(), None,
-                                               qg.data_ptr(), _lib.stream_ptr()), "swarm_q_forward")
+            _lib.call(eng.lib, "swarm_q_forward", eng.cfg, eng.params.data_ptr(), xg.data_ptr(), None, qg.data_ptr())
             torch.cuda.synchronize()
             qg = qg.cpu().reshape(512, N, 9).double()
             ulp = torch.from_numpy(np.spacing(np.abs(q64.numpy()).astype(np.float32)).astype(np.float64))
