@@ -10,18 +10,16 @@
 //
 // Per wave: dl_forward on x (graph built from x[:, :2] for kNN / radius, the caller's
 // multiplicities for dense) with T / R kept, then
-//   dR = W2^T dq ; dZ = dR * [Z > 0] ; dT = W1^T dZ ; dO = dT * (1 - t^2)
-//   GAT: g_uv = dO_v.h_u ; de_uv = c_uv (g_uv - sum_w c_wv g_wv) ; dp = de * leaky'(p)
-//        da_dst[v] = sum_u dp_uv ; da_src[u] = sum_v dp_uv ; dh_u = sum_v c_uv dO_v + da_src att_src + da_dst att_dst
+//   dR = W2^T dq ; dZ = dR * [Z > 0]            (here: the full 9-action dq row)
+//   dO, the attention's dp / da_dst, dh: swarm_bwd.h, the TD kernel's own
 //   GCNConv: dh_u = sum_v c_uv dO_v (the normalisation holds no parameter)
-// c_uv carries the edge multiplicity; a target without an in-edge has c_uv = 0 for every u and
-// adds nothing (no exp is evaluated in the backward).  After one block barrier the parameter
-// products over the block's 32 rows, dW1 = dZ^T T, dW2 = dq^T R, dW = dh^T X on MFMA 16x16x4
-// (node index as K), the vectors as ordered LDS column sums.  Every block writes every column
-// 0..N_PARAMS of its slab (column N_PARAMS: 0), so the workspace need not be zeroed; rows of
-// graphs past B and slots past N enter every sum as zeros.  No atomics: bitwise reproducible.
+// After one block barrier the parameter products over the block's 32 rows, dW1 = dZ^T T,
+// dW2 = dq^T R (here), dW = dh^T X and the vectors' ordered column sums (swarm_bwd.h).  Every
+// block writes every column 0..N_PARAMS of its slab (column N_PARAMS: 0), so the workspace need
+// not be zeroed; rows of graphs past B and slots past N enter every sum as zeros.  No atomics:
+// bitwise reproducible.
 #pragma once
-#include "swarm_tdk.h"
+#include "swarm_bwd.h"
 
 namespace swarm {
 
@@ -116,8 +114,7 @@ __device__ __forceinline__ void qbk_body(QbSmem<NS>& L, const int vb, const QbAr
 #pragma unroll
       for (int r = 0; r < 4; ++r) dz[ct][t][r] = (nv[ct] && F.zr[ct][t][r] > 0.0f) ? dr[t][r] : 0.0f;
     const int row = row0 + 16 * ct + c;
-    *reinterpret_cast<float4*>(&TB.dZ[row][4 * p]) = make_float4(dz[ct][0][0], dz[ct][0][1], dz[ct][0][2], dz[ct][0][3]);
-    *reinterpret_cast<float4*>(&TB.dZ[row][16 + 4 * p]) = make_float4(dz[ct][1][0], dz[ct][1][1], dz[ct][1][2], dz[ct][1][3]);
+    row_store(TB.dZ[row], p, dz[ct]);
     TB.X[row][p] = F.x[ct][0];
     TB.X[row][4 + p] = F.x[ct][1];
 #pragma unroll
@@ -132,137 +129,28 @@ __device__ __forceinline__ void qbk_body(QbSmem<NS>& L, const int vb, const QbAr
     }
   }
 
-  // ---- dT^T = W1^T dZ^T on MFMA (the dz registers are the B operand), dO = dT * (1 - t^2)
+  // ---- the per-node backward (swarm_bwd.h): dO, the attention's dp / da_dst, dh
   float dO[CT][2][4];
 #pragma unroll
   for (int ct = 0; ct < CT; ++ct) {
-    float w1f[2][2][4];
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int t2 = 0; t2 < 2; ++t2) w1f[t2][t][r] = P[L_W1 + (16 * t + 4 * p + r) * kWRow + 16 * t2 + c];
-    f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int t2 = 0; t2 < 2; ++t2) acc[t2] = mfma16(w1f[t2][t][r], dz[ct][t][r], acc[t2]);
-#pragma unroll
-    for (int t2 = 0; t2 < 2; ++t2)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        dO[ct][t2][r] = nv[ct] ? acc[t2][r] * (1.0f - F.t[ct][t2][r] * F.t[ct][t2][r]) : 0.0f;
-    const int row = row0 + 16 * ct + c;
-    *reinterpret_cast<float4*>(&TB.dO[row][4 * p]) = make_float4(dO[ct][0][0], dO[ct][0][1], dO[ct][0][2], dO[ct][0][3]);
-    *reinterpret_cast<float4*>(&TB.dO[row][16 + 4 * p]) = make_float4(dO[ct][1][0], dO[ct][1][1], dO[ct][1][2], dO[ct][1][3]);
+    bwd_dO_tile(P, c, p, dz[ct], F.t[ct], nv[ct], dO[ct]);
+    row_store(TB.dO[row0 + 16 * ct + c], p, dO[ct]);
   }
-  // ---- GAT backward (attention part).  g[u][v] = H_u . dO_v on MFMA (A = H rows, B = the dO
-  //      registers); lane (c, p) holds g[u = 16 ut + 4 p + r][v = 16 ct + c]
   float da_d[CT];
 #pragma unroll
   for (int ct = 0; ct < CT; ++ct) da_d[ct] = 0.0f;
-  WSmall<NS>& sm = *V.sm;
   if (conv == SWARM_CONV_GAT) {
-    float ah[CT][2][4];
+    float dp[CT][CT][4];
+    bwd_attention<NS>(TB.H + row0, F, V.sm->ssrc, dO, nv, c, p, dp, da_d);
 #pragma unroll
-    for (int ut = 0; ut < CT; ++ut) {
-      const int u = 16 * ut + c;
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const float4 hv = *reinterpret_cast<const float4*>(&TB.H[row0 + u][16 * t + 4 * p]);
-        ah[ut][t][0] = hv.x; ah[ut][t][1] = hv.y; ah[ut][t][2] = hv.z; ah[ut][t][3] = hv.w;
-      }
-    }
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct) {
-      const int v = 16 * ct + c;
-      float gv[CT][4], cu[CT][4];
-      float part = 0.0f;
-#pragma unroll
-      for (int ut = 0; ut < CT; ++ut) {
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) acc = mfma16(ah[ut][t][r], dO[ct][t][r], acc);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          // coefficient of edge u -> v, u = 16 ut + 4 p + r (registers hold every u of target v)
-          float cc[4];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) cc[q] = F.cf[ct][16 * ut + 4 * q + r];
-          cu[ut][r] = p == 0 ? cc[0] : (p == 1 ? cc[1] : (p == 2 ? cc[2] : cc[3]));
-          gv[ut][r] = acc[r];
-          part = part + cu[ut][r] * gv[ut][r];
-        }
-      }
-      const float Gs = row4_sum(part);
-      float dsum = 0.0f;
+    for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
       for (int ut = 0; ut < CT; ++ut)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int u = 16 * ut + 4 * p + r;
-          float dpu = 0.0f;
-          if (cu[ut][r] != 0.0f && nv[ct]) {   // in-edges only (cross-graph / absent: c = 0)
-            const float de = cu[ut][r] * (gv[ut][r] - Gs);
-            const float pre = sm.ssrc[u] + F.sdst[ct];
-            dpu = pre > 0.0f ? de : de * kLeakySlope;
-          }
-          dsum = dsum + dpu;
-          TB.dp[row0 + v][u] = dpu;
-        }
-      da_d[ct] = row4_sum(dsum);
-    }
+        for (int r = 0; r < 4; ++r) TB.dp[row0 + 16 * ct + c][16 * ut + 4 * p + r] = dp[ct][ut][r];
   }
   wave_lds_sync();   // cm / dp / dO rows of this wave's graphs
-  // ---- dh_u = sum_v c[v][u] dO_v (MFMA: A = dO rows, B = C column) + da_src att_src + da_dst att_dst
-  {
-    const float4 s0 = *reinterpret_cast<const float4*>(P + L_ATT_SRC + 4 * p);
-    const float4 s1 = *reinterpret_cast<const float4*>(P + L_ATT_SRC + 16 + 4 * p);
-    const float4 d0 = *reinterpret_cast<const float4*>(P + L_ATT_DST + 4 * p);
-    const float4 d1 = *reinterpret_cast<const float4*>(P + L_ATT_DST + 16 + 4 * p);
-    const float as[2][4] = {{s0.x, s0.y, s0.z, s0.w}, {s1.x, s1.y, s1.z, s1.w}};
-    const float ad[2][4] = {{d0.x, d0.y, d0.z, d0.w}, {d1.x, d1.y, d1.z, d1.w}};
-    float ao[2][NS / 4];
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int ks = 0; ks < NS / 4; ++ks) ao[t][ks] = TB.dO[row0 + 4 * ks + p][16 * t + c];
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct) {
-      const int u = 16 * ct + c;
-      float da_s = 0.0f;
-      if (conv == SWARM_CONV_GAT) {   // sum over the targets v of u's own graph, in order
-        const int base = (GS < NS) ? (u / GS) * GS : 0;
-        float dpj[GS];
-#pragma unroll
-        for (int j = 0; j < GS; ++j) dpj[j] = TB.dp[row0 + base + j][u];
-#pragma unroll
-        for (int j = 0; j < GS; ++j) da_s = j < N ? da_s + dpj[j] : da_s;
-      }
-      const float das = nv[ct] ? da_s : 0.0f, dad = nv[ct] ? da_d[ct] : 0.0f;
-      f32x4 m0 = {0.f, 0.f, 0.f, 0.f}, m1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < NS / 4; ++ks) {
-        const float b = TB.cm[row0 + 4 * ks + p][u];
-        m0 = mfma16(ao[0][ks], b, m0);
-        m1 = mfma16(ao[1][ks], b, m1);
-      }
-      float dh[2][4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        dh[0][r] = nv[ct] ? (m0[r] + das * as[0][r]) + dad * ad[0][r] : 0.0f;
-        dh[1][r] = nv[ct] ? (m1[r] + das * as[1][r]) + dad * ad[1][r] : 0.0f;
-      }
-      *reinterpret_cast<float4*>(&TB.dH[row0 + u][4 * p]) = make_float4(dh[0][0], dh[0][1], dh[0][2], dh[0][3]);
-      *reinterpret_cast<float4*>(&TB.dH[row0 + u][16 + 4 * p]) = make_float4(dh[1][0], dh[1][1], dh[1][2], dh[1][3]);
-      if (p == 0) { TB.das[row0 + u] = das; TB.dad[row0 + u] = dad; }
-    }
-  }
+  bwd_dh<NS, GS>(TB, P, row0, N, conv, nv, da_d, c, p);
   __syncthreads();   // every wave's dZ / T / R / DQ / X / dO / dH / das / dad rows
 
   // ---- parameter products over the block's 32 rows, spread over its waves; each job writes its
@@ -301,38 +189,19 @@ __device__ __forceinline__ void qbk_body(QbSmem<NS>& L, const int vb, const QbAr
       }
     } else if (job < 4) {
       const int t = job - 2;
-      float ha[kTdRows / 4], xb[kTdRows / 4];   // column 8 of X is +0: the padding columns read it
-#pragma unroll
-      for (int ks = 0; ks < kTdRows / 4; ++ks) {
-        const int n = 4 * ks + p;
-        ha[ks] = TB.dH[n][16 * t + c];
-        xb[ks] = TB.X[n][c < kFeat ? c : 8];
-      }
-      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < kTdRows / 4; ++ks) acc = mfma16(ha[ks], xb[ks], acc);
+      const f32x4 acc = bwd_dw_tile(TB, t, c, p);
       if (c < kFeat) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) sst(OFF_W + (16 * t + 4 * p + r) * kFeat + c, acc[r]);
       }
     } else if (job == 4) {
-      const float(*src)[kRow] = h == 0 ? TB.dZ : TB.dO;
-      float acc = src[0][col];
-#pragma unroll
-      for (int n = 1; n < kTdRows; ++n) acc = acc + src[n][col];
-      sst((h == 0 ? OFF_B1 : OFF_BIAS) + col, acc);
-    } else if (job == 5) {   // att_src (half 0) / att_dst (half 1): sum_n da[n] H[n][col]; GCNConv: none
-      const float* da = h == 0 ? TB.das : TB.dad;
-      float acc = da[0] * TB.H[0][col];
-#pragma unroll
-      for (int n = 1; n < kTdRows; ++n) acc = acc + da[n] * TB.H[n][col];
+      sst((h == 0 ? OFF_B1 : OFF_BIAS) + col, col_sum32(h == 0 ? TB.dZ : TB.dO, col));
+    } else if (job == 5) {   // att_src (half 0) / att_dst (half 1); GCNConv: none (the sum can be -0)
+      const float acc = bwd_att_col(TB, h == 0 ? TB.das : TB.dad, col);
       sst((h == 0 ? OFF_ATT_SRC : OFF_ATT_DST) + col, conv == SWARM_CONV_GAT ? acc : 0.0f);
     } else {
       if (lane < kActions) {
-        float acc = L.DQ[0][lane];
-#pragma unroll
-        for (int n = 1; n < kTdRows; ++n) acc = acc + L.DQ[n][lane];
-        sst(OFF_B2 + lane, acc);
+        sst(OFF_B2 + lane, col_sum32(L.DQ, lane));
       } else if (lane == 63) {
         sst(N_PARAMS, 0.0f);
       }

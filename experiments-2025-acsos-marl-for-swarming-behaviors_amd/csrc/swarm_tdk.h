@@ -5,59 +5,21 @@
 // Reference: DQNTrainer.train_step_dqn (src/training/train_gcn_dqn.py:112-137),
 // GraphReplayBuffer.sample (:38-45), Adam(lr=1e-3) (:85), target sync (:131-133).
 //
-// Layout (swarm_wpg.h): one wave per sampled graph; a block holds 32 node slots.
+// Layout (swarm_wpg.h): one wave per sampled graph; a block holds 32 node slots (swarm_bwd.h TdLds).
 // Backward per graph (online wave, per-node vectors in registers):
 //   dQ[a] = (Q[a]-y) * 2/M                      (MSELoss mean, gather)
-//   dR = W2[a]^T dQ ; dZ = dR * [Z>0] ; dT = W1^T dZ ; dOut = dT * (1 - t^2)
-//   GAT: g_uv = dOut_v.h_u ; de_uv = c_uv (g_uv - sum_w c_wv g_wv) ; dp = de * leaky'(p)
-//        da_dst[v] = sum_u dp_uv ; da_src[u] = sum_v dp_uv ; dh_u = sum_v c_uv dOut_v + da_src att_src + da_dst att_dst
-// Parameter sums over the block's 32 node rows: dW1 = dZ^T T, dW2 = dQ^T R, dW = dh^T X on
-// MFMA (16x16x4 f32 tiles, node index as K), vectors by LDS column sums; each block writes one
-// slab [N_PARAMS + 1] (last = sum of squared TD errors) and swarm_grad_reduce sums the
-// slabs in a fixed order (bitwise run-to-run reproducible).
+//   dR = W2[a]^T dQ ; dZ = dR * [Z>0]           (here: the one-hot dQ of the TD loss)
+//   dO, the attention's dp / da_dst, dh: swarm_bwd.h, shared with swarm_q_backward (swarm_qbk.h)
+// Parameter sums over the block's 32 node rows: dW1 = dZ^T T, dW2 = dQ^T R (here), dW = dh^T X and
+// the vectors' ordered column sums (swarm_bwd.h); each block writes one slab [N_PARAMS + 1]
+// (last = sum of squared TD errors) and swarm_grad_reduce sums the slabs in a fixed order
+// (bitwise run-to-run reproducible).
 #pragma once
 #include "swarm_adam.h"
+#include "swarm_bwd.h"
 #include "swarm_diag.h"
-#include "swarm_dl.h"
 
 namespace swarm {
-
-// One TD block = 32 node slots = GPB = 32 / NS sampled graphs.  Wave w < GPB runs the
-// ONLINE network on graph w (forward on s with activations kept, dQ, backward of the
-// per-node vectors); wave GPB + w runs the TARGET network on s' of graph w
-// (y = r + gamma max_a Q_tgt), then shares the parameter products.  The parameter
-// gradient of the block is a sum over its 32 node rows: MFMA 16x16x4 f32 tiles with the
-// node index as K, spread over the waves, each writing its slice of the slab.
-constexpr int kTdRows = 32;
-
-template <int NS>
-struct TdLds {
-  static constexpr int GPB = kTdRows / NS;
-  float H[kTdRows][kRow];         // online conv1.lin output
-  float T[kTdRows][kRow];         // tanh(conv out)
-  float R[kTdRows][kRow];         // relu(lin1)
-  // written only after B1; before it, rows NS w .. NS w + NS - 1 of dZ / dO / dH are target
-  // wave w's forward scratch (its H / T / R rows): 13.8 KB less LDS per block, so three
-  // 256-thread blocks fit a CU (the fused tick at N = 9..16 has 3 blocks per CU)
-  float dZ[kTdRows][kRow];        // dL/d lin1 pre-activation
-  float dO[kTdRows][kRow];        // dL/d conv out
-  float dH[kTdRows][kRow];        // dL/d h
-  float X[kTdRows][9];            // node features (k < 8)
-  union {
-    struct {
-      float cm[kTdRows][NS + 1];  // c[target row][source slot]
-      float dp[kTdRows][NS + 1];  // dL/d pre-activation of edge (source -> target row)
-    };
-    WSmall<NS> tgsm[GPB];         // before B1: the target waves' small scratch
-  };
-  float yq[kTdRows], gq[kTdRows], das[kTdRows], dad[kTdRows], d2[kTdRows];   // yq: gamma max_a Q_target(s')
-  int act[kTdRows];
-  int tdrop[kTdRows];             // fused tick: the target wave dropped this row's graph (hand-off overrun)
-  int prew[GPB];                  // online wave w is on the pre path (swarm_tdk.h td_body)
-  int insl[GPB];                  // before B0: online wave w holds a graph of this tick's slot
-  WSmall<NS> on[GPB];             // online waves' per-graph scratch
-  __device__ WView<NS> target_view(int w) { return WView<NS>{dZ + NS * w, dO + NS * w, dH + NS * w, &tgsm[w]}; }
-};
 
 struct TdArgs {
   int S, B, N, graph, k, conv, env_offset;
@@ -163,6 +125,7 @@ __device__ __forceinline__ void td_body(TdSmem<NS>& L, const int vb, const int32
   constexpr int NT = 128 * GPB;
   static_assert(!FUSED || NT == kAdamNT, "the fused TD block is one Adam workgroup");
   static_assert(GPB <= 2, "B2 jobs 2 and 3 go to the pre-path online waves by wave index (GPB <= 2)");
+  static_assert(NS % 16 == 0, "every MFMA column of a wave is one of its node slots");
   TdLds<NS>& TB = L.TB;
   float* Pon = L.Pon;
   float* Ptg = L.Ptg;
@@ -182,7 +145,7 @@ __device__ __forceinline__ void td_body(TdSmem<NS>& L, const int vb, const int32
   float* const slab_base = A.slabs + (size_t)vb * kSlabCols;
   const uint32_t slab_stride = (uint32_t)A.n_slabs * kSlabCols;
   TD_DIAG_SLAB_STATE   // swarm_diag.h: nothing, and every block stores, in the product build
-  auto sst_g = [&](int q, float v) {
+  auto sst = [&](int q, float v) {
     if (TD_DIAG_STORES_SLAB(vb)) slab_st(slab_base + ((uint32_t)(q >> 4) * slab_stride + (uint32_t)(q & 15)), v);
   };
 // the dW1 / dW2 tiles' 16-B pieces: four consecutive parameters q .. q + 3 (q % 4 == 0) of one
@@ -194,7 +157,6 @@ __device__ __forceinline__ void td_body(TdSmem<NS>& L, const int vb, const int32
     if (!TD_DIAG_STORES_SLAB(vb)) return;
     st16_wt(slab_base + ((uint32_t)(q >> 4) * slab_stride + (uint32_t)(q & 15)), v[0], v[1], v[2], v[3]);
   };
-  auto sst = sst_g;
   SWARM_RTSTAMP(8);
   SWARM_STAMP(0);
 
@@ -233,7 +195,7 @@ __device__ __forceinline__ void td_body(TdSmem<NS>& L, const int vb, const int32
     const int gi = (GS < NS) ? n / GS : 0;
     jl[ct] = (GS < NS) ? n % GS : n;
     sid[ct] = vb * (kTdRows / GS) + wi * GPW + gi;
-    live[ct] = sid[ct] < S && n < NS;
+    live[ct] = sid[ct] < S;
     nv[ct] = live[ct] && jl[ct] < N;
     gid[ct] = 0;
     if (!FUSED && sample_in) gid[ct] = min((uint32_t)sample_in[min(sid[ct], S - 1)], ring_graphs - 1u);
@@ -284,7 +246,7 @@ __device__ __forceinline__ void td_body(TdSmem<NS>& L, const int vb, const int32
   }
   // ---- skip while the replay holds fewer than `batch` graphs (train_gcn_dqn.py:113-115)
   if (n_graphs < (uint32_t)S) {
-    for (int q = threadIdx.x; q <= N_PARAMS; q += NT) sst_g(q, 0.0f);
+    for (int q = threadIdx.x; q <= N_PARAMS; q += NT) sst(q, 0.0f);
     return;
   }
   if (sample_out && online && p == 0) {
@@ -320,13 +282,11 @@ __device__ __forceinline__ void td_body(TdSmem<NS>& L, const int vb, const int32
   }
   if (online && p == 0 && !waited) {
 #pragma unroll
-    for (int ct = 0; ct < CT; ++ct)
-      if (16 * ct + c < NS) TB.act[row0 + 16 * ct + c] = act[ct];
+    for (int ct = 0; ct < CT; ++ct) TB.act[row0 + 16 * ct + c] = act[ct];
   }
   if (FUSED && !online && p == 0) {   // no graph dropped yet (set by an s' overrun, read by the r wait)
 #pragma unroll
-    for (int ct = 0; ct < CT; ++ct)
-      if (16 * ct + c < NS) TB.tdrop[row0 + 16 * ct + c] = 0;
+    for (int ct = 0; ct < CT; ++ct) TB.tdrop[row0 + 16 * ct + c] = 0;
   }
   __syncthreads();   // B0: weight images
   SWARM_STAMP(2);
@@ -374,7 +334,7 @@ __device__ __forceinline__ void td_body(TdSmem<NS>& L, const int vb, const int32
         if (FUSED && !online && p == 0) {
 #pragma unroll
           for (int ct = 0; ct < CT; ++ct)
-            if (16 * ct + c < NS && live_drop[ct]) *(volatile int*)&TB.tdrop[row0 + 16 * ct + c] = 1;
+            if (live_drop[ct]) *(volatile int*)&TB.tdrop[row0 + 16 * ct + c] = 1;
         }
         if (lane == 0) atomicAdd(X.ho_err, 1u);
         break;
@@ -420,8 +380,7 @@ __device__ __forceinline__ void td_body(TdSmem<NS>& L, const int vb, const int32
     }
     if (p == 0) {
 #pragma unroll
-      for (int ct = 0; ct < CT; ++ct)
-        if (16 * ct + c < NS) TB.act[row0 + 16 * ct + c] = nv[ct] ? act[ct] : 0;
+      for (int ct = 0; ct < CT; ++ct) TB.act[row0 + 16 * ct + c] = nv[ct] ? act[ct] : 0;
     }
   }
   // ---- pre path, before y: dZ1 = W2[a] * [z > 0], dO1 = (W1^T dZ1) (1 - t^2) (MFMA, as after B2),
@@ -440,84 +399,14 @@ __device__ __forceinline__ void td_body(TdSmem<NS>& L, const int vb, const int32
 #pragma unroll
         for (int r = 0; r < 4; ++r) dz1[t][r] = F.zr[ct][t][r] > 0.0f ? wv[r] : 0.0f;
       }
-      float w1f[2][2][4];
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-          for (int t2 = 0; t2 < 2; ++t2) w1f[t2][t][r] = Pon[L_W1 + (16 * t + 4 * p + r) * kWRow + 16 * t2 + c];
-      f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-          for (int t2 = 0; t2 < 2; ++t2) acc[t2] = mfma16(w1f[t2][t][r], dz1[t][r], acc[t2]);
-#pragma unroll
-      for (int t2 = 0; t2 < 2; ++t2)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) dO1[ct][t2][r] = acc[t2][r] * (1.0f - F.t[ct][t2][r] * F.t[ct][t2][r]);
+      bwd_dO_tile(Pon, c, p, dz1, F.t[ct], true, dO1[ct]);
       dad1[ct] = 0.0f;
-#pragma unroll
-      for (int ut = 0; ut < CT; ++ut)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) dp1[ct][ut][r] = 0.0f;
     }
-    if (conv == SWARM_CONV_GAT) {
-      const WSmall<NS>& sm = *V.sm;
-      float ah[CT][2][4];
+    if (conv == SWARM_CONV_GAT) {   // unmasked: nv (as known after B1) is applied there, with gq
+      bool all[CT];
 #pragma unroll
-      for (int ut = 0; ut < CT; ++ut) {
-        const int u = min(16 * ut + c, NS - 1);
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          const float4 hv = *reinterpret_cast<const float4*>(&TB.H[row0 + u][16 * t + 4 * p]);
-          ah[ut][t][0] = hv.x; ah[ut][t][1] = hv.y; ah[ut][t][2] = hv.z; ah[ut][t][3] = hv.w;
-        }
-      }
-#pragma unroll
-      for (int ct = 0; ct < CT; ++ct) {
-        float gv[CT][4], cu[CT][4];
-        float part = 0.0f;
-#pragma unroll
-        for (int ut = 0; ut < CT; ++ut) {
-          f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-          for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc = mfma16(ah[ut][t][r], dO1[ct][t][r], acc);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            float cc4[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              const int uq = 16 * ut + 4 * q + r;
-              cc4[q] = uq < NS ? F.cf[ct][uq < NS ? uq : 0] : 0.0f;
-            }
-            cu[ut][r] = p == 0 ? cc4[0] : (p == 1 ? cc4[1] : (p == 2 ? cc4[2] : cc4[3]));
-            gv[ut][r] = acc[r];
-            part = part + cu[ut][r] * gv[ut][r];
-          }
-        }
-        const float Gs = row4_sum(part);
-        float dsum = 0.0f;
-#pragma unroll
-        for (int ut = 0; ut < CT; ++ut)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int u = 16 * ut + 4 * p + r;
-            float dpu = 0.0f;
-            if (u < NS && cu[ut][r] != 0.0f) {   // in-edges only (cross-graph / absent: c = 0)
-              const float de = cu[ut][r] * (gv[ut][r] - Gs);
-              const float pre_act = sm.ssrc[u] + F.sdst[ct];
-              dpu = pre_act > 0.0f ? de : de * kLeakySlope;
-            }
-            dsum = dsum + dpu;
-            dp1[ct][ut][r] = dpu;
-          }
-        dad1[ct] = row4_sum(dsum);
-      }
+      for (int ct = 0; ct < CT; ++ct) all[ct] = true;
+      bwd_attention<NS>(TB.H + row0, F, V.sm->ssrc, dO1, all, c, p, dp1, dad1);
     }
   }
   if (FUSED && waited && online) {   // r of this tick's transitions (y = r + gamma max Q_tgt after B1)
@@ -540,7 +429,7 @@ __device__ __forceinline__ void td_body(TdSmem<NS>& L, const int vb, const int32
         bool rest = false;
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct) {
-          if (!okc[ct] && *(volatile int*)&TB.tdrop[row0 + min(16 * ct + c, NS - 1)] != 0) {
+          if (!okc[ct] && *(volatile int*)&TB.tdrop[row0 + 16 * ct + c] != 0) {
             okc[ct] = true;
             live_drop[ct] = true;
             nv[ct] = false;
@@ -562,10 +451,8 @@ __device__ __forceinline__ void td_body(TdSmem<NS>& L, const int vb, const int32
       float qmax = F.q[ct][0];
 #pragma unroll
       for (int a = 1; a < kActions; ++a) qmax = fmaxf(qmax, F.q[ct][a]);
-      if (16 * ct + c < NS) {
-        TB.yq[row0 + 16 * ct + c] = nv[ct] ? A.gamma * qmax : 0.0f;   // y = r + this (online waves)
-        if (FUSED) TB.tdrop[row0 + 16 * ct + c] = live_drop[ct] ? 1 : 0;
-      }
+      TB.yq[row0 + 16 * ct + c] = nv[ct] ? A.gamma * qmax : 0.0f;   // y = r + this (online waves)
+      if (FUSED) TB.tdrop[row0 + 16 * ct + c] = live_drop[ct] ? 1 : 0;
     }
   }
   if (!online && !waited) __builtin_amdgcn_s_setprio(0);
@@ -580,12 +467,12 @@ __device__ __forceinline__ void td_body(TdSmem<NS>& L, const int vb, const int32
     // ---- dQ at the taken action (MSELoss mean), dR = W2[a]^T dQ, dZ = dR * [z > 0]
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) {
-      const int n = 16 * ct + c, nn = min(n, NS - 1);
-      if (FUSED && TB.tdrop[row0 + nn]) nv[ct] = false;   // the target wave dropped the graph
+      const int row = row0 + 16 * ct + c;
+      if (FUSED && TB.tdrop[row]) nv[ct] = false;   // the target wave dropped the graph
       float qa = F.q[ct][0];
 #pragma unroll
       for (int a = 1; a < kActions; ++a) qa = (act[ct] == a) ? F.q[ct][a] : qa;
-      const float delta = nv[ct] ? (qa - (rew[ct] + TB.yq[row0 + nn])) : 0.0f;   // y = r + gamma max Q_tgt(s')
+      const float delta = nv[ct] ? (qa - (rew[ct] + TB.yq[row])) : 0.0f;   // y = r + gamma max Q_tgt(s')
       const float gq = delta * A.grad_scale;
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
@@ -595,34 +482,24 @@ __device__ __forceinline__ void td_body(TdSmem<NS>& L, const int vb, const int32
 #pragma unroll
         for (int r = 0; r < 4; ++r) dz[ct][t][r] = F.zr[ct][t][r] > 0.0f ? wv[r] * gq : 0.0f;
       }
-      if (n < NS) {
-        const int row = row0 + n;
-        *reinterpret_cast<float4*>(&TB.dZ[row][4 * p]) = make_float4(dz[ct][0][0], dz[ct][0][1], dz[ct][0][2], dz[ct][0][3]);
-        *reinterpret_cast<float4*>(&TB.dZ[row][16 + 4 * p]) = make_float4(dz[ct][1][0], dz[ct][1][1], dz[ct][1][2], dz[ct][1][3]);
-        TB.X[row][p] = F.x[ct][0];
-        TB.X[row][4 + p] = F.x[ct][1];
+      row_store(TB.dZ[row], p, dz[ct]);
+      TB.X[row][p] = F.x[ct][0];
+      TB.X[row][4 + p] = F.x[ct][1];
 #pragma unroll
-        for (int j = 0; j < NS / 4; ++j) TB.cm[row][4 * j + p] = pick4(F.cf[ct], j, p);
-        if (p == 0) { TB.X[row][8] = 0.0f; TB.gq[row] = gq; TB.d2[row] = delta * delta; }
-      }
+      for (int j = 0; j < NS / 4; ++j) TB.cm[row][4 * j + p] = pick4(F.cf[ct], j, p);
+      if (p == 0) { TB.X[row][8] = 0.0f; TB.gq[row] = gq; TB.d2[row] = delta * delta; }
       if (pre) {   // the pre path's images scaled by this node's gq (rows free since B1)
         float o[2][4];
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
           for (int r = 0; r < 4; ++r) o[t][r] = nv[ct] ? dO1[ct][t][r] * gq : 0.0f;
-        if (n < NS) {
-          *reinterpret_cast<float4*>(&TB.dO[row0 + n][4 * p]) = make_float4(o[0][0], o[0][1], o[0][2], o[0][3]);
-          *reinterpret_cast<float4*>(&TB.dO[row0 + n][16 + 4 * p]) = make_float4(o[1][0], o[1][1], o[1][2], o[1][3]);
-          if (conv == SWARM_CONV_GAT) {
+        row_store(TB.dO[row], p, o);
+        if (conv == SWARM_CONV_GAT) {
 #pragma unroll
-            for (int ut = 0; ut < CT; ++ut)
+          for (int ut = 0; ut < CT; ++ut)
 #pragma unroll
-              for (int r = 0; r < 4; ++r) {
-                const int u = 16 * ut + 4 * p + r;
-                if (u < NS) TB.dp[row0 + n][u] = nv[ct] ? dp1[ct][ut][r] * gq : 0.0f;
-              }
-          }
+            for (int r = 0; r < 4; ++r) TB.dp[row][16 * ut + 4 * p + r] = nv[ct] ? dp1[ct][ut][r] * gq : 0.0f;
         }
         dad1[ct] = nv[ct] ? dad1[ct] * gq : 0.0f;
       }
@@ -671,15 +548,7 @@ __device__ __forceinline__ void td_body(TdSmem<NS>& L, const int vb, const int32
   };
   auto b2_job = [&](int job) {   // the vector sums: job 2 = db1, job 3 = db2 and the loss
     if (job == 2) {
-      if (lane < kHidden) {
-        float v[kTdRows];
-#pragma unroll
-        for (int n = 0; n < kTdRows; ++n) v[n] = TB.dZ[n][lane];
-        float acc = v[0];
-#pragma unroll
-        for (int n = 1; n < kTdRows; ++n) acc = acc + v[n];
-        sst(OFF_B1 + lane, acc);
-      }
+      if (lane < kHidden) sst(OFF_B1 + lane, col_sum32(TB.dZ, lane));
     } else if (lane < kActions || lane == 63) {   // db2 / loss: the ordered sum over the 32 rows,
       // 8 rows' reads at a time (each read unconditional: as selects around the reads they became
       // a branch and an LDS round trip per row)
@@ -704,150 +573,33 @@ __device__ __forceinline__ void td_body(TdSmem<NS>& L, const int vb, const int32
 
   const int col = lane & 31, h = lane >> 5;
   if (online) {
+    // ---- the per-node backward (swarm_bwd.h).  A pre-path wave has its dO / dp rows and da_dst
+    //      since B1 and joins at dh, the step that mixes targets
     float da_d[CT];
-    WSmall<NS>& sm = *V.sm;
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) da_d[ct] = pre ? dad1[ct] : 0.0f;
     if (!pre) {
-    // ---- dT^T = W1^T dZ^T on MFMA (the dz registers are the B operand),
-    //      dO = dT * (1 - t^2) with the forward's tanh registers
-    float dO[CT][2][4];
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct) {
-      const int n = 16 * ct + c;
-      // W1 fragments first (16 LDS reads in flight), then the two output tiles' chains interleaved
-      float w1f[2][2][4];
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-          for (int t2 = 0; t2 < 2; ++t2) w1f[t2][t][r] = P[L_W1 + (16 * t + 4 * p + r) * kWRow + 16 * t2 + c];
-      f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-          for (int t2 = 0; t2 < 2; ++t2) acc[t2] = mfma16(w1f[t2][t][r], dz[ct][t][r], acc[t2]);
-#pragma unroll
-      for (int t2 = 0; t2 < 2; ++t2)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          dO[ct][t2][r] = nv[ct] ? acc[t2][r] * (1.0f - F.t[ct][t2][r] * F.t[ct][t2][r]) : 0.0f;
-      if (n < NS) {
-        *reinterpret_cast<float4*>(&TB.dO[row0 + n][4 * p]) = make_float4(dO[ct][0][0], dO[ct][0][1], dO[ct][0][2], dO[ct][0][3]);
-        *reinterpret_cast<float4*>(&TB.dO[row0 + n][16 + 4 * p]) = make_float4(dO[ct][1][0], dO[ct][1][1], dO[ct][1][2], dO[ct][1][3]);
-      }
-    }
-    SWARM_STAMP(24);
-    // ---- GAT backward (attention part).  g[u][v] = H_u . dO_v on MFMA (A = H rows,
-    //      B = the dO registers); lane (c, p) holds g[u = 16 ut + 4 p + r][v = 16 ct + c]
-    if (conv == SWARM_CONV_GAT) {
-      float ah[CT][2][4];
-#pragma unroll
-      for (int ut = 0; ut < CT; ++ut) {
-        const int u = min(16 * ut + c, NS - 1);
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          const float4 hv = *reinterpret_cast<const float4*>(&TB.H[row0 + u][16 * t + 4 * p]);
-          ah[ut][t][0] = hv.x; ah[ut][t][1] = hv.y; ah[ut][t][2] = hv.z; ah[ut][t][3] = hv.w;
-        }
-      }
+      float dO[CT][2][4];
 #pragma unroll
       for (int ct = 0; ct < CT; ++ct) {
-        const int v = 16 * ct + c;
-        float gv[CT][4], cu[CT][4];
-        float part = 0.0f;
-#pragma unroll
-        for (int ut = 0; ut < CT; ++ut) {
-          f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-          for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc = mfma16(ah[ut][t][r], dO[ct][t][r], acc);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            // coefficient of edge u -> v, u = 16 ut + 4 p + r (registers hold every u of target v)
-            float cc[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              const int uq = 16 * ut + 4 * q + r;
-              cc[q] = uq < NS ? F.cf[ct][uq < NS ? uq : 0] : 0.0f;
-            }
-            cu[ut][r] = p == 0 ? cc[0] : (p == 1 ? cc[1] : (p == 2 ? cc[2] : cc[3]));
-            gv[ut][r] = acc[r];
-            part = part + cu[ut][r] * gv[ut][r];
-          }
-        }
-        const float Gs = row4_sum(part);
-        float dsum = 0.0f;
-#pragma unroll
-        for (int ut = 0; ut < CT; ++ut)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int u = 16 * ut + 4 * p + r;
-            float dpu = 0.0f;
-            if (u < NS && cu[ut][r] != 0.0f && nv[ct]) {   // in-edges only (cross-graph / absent: c = 0)
-              const float de = cu[ut][r] * (gv[ut][r] - Gs);
-              const float pre = sm.ssrc[u] + F.sdst[ct];
-              dpu = pre > 0.0f ? de : de * kLeakySlope;
-            }
-            dsum = dsum + dpu;
-            if (u < NS && v < NS) TB.dp[row0 + v][u] = dpu;
-          }
-        da_d[ct] = row4_sum(dsum);
+        bwd_dO_tile(P, c, p, dz[ct], F.t[ct], nv[ct], dO[ct]);
+        row_store(TB.dO[row0 + 16 * ct + c], p, dO[ct]);
       }
+      SWARM_STAMP(24);
+      if (conv == SWARM_CONV_GAT) {
+        float dp[CT][CT][4];
+        bwd_attention<NS>(TB.H + row0, F, V.sm->ssrc, dO, nv, c, p, dp, da_d);
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+          for (int ut = 0; ut < CT; ++ut)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) TB.dp[row0 + 16 * ct + c][16 * ut + 4 * p + r] = dp[ct][ut][r];
+      }
+      wave_lds_sync();   // dp / dO rows of this graph
     }
-    wave_lds_sync();   // dp / dO rows of this graph
-    }   // !pre
     SWARM_STAMP(25);
-    // ---- dh_u = sum_v c[v][u] dO_v (MFMA: A = dO rows, B = C column) + da_src att_src + da_dst att_dst
-    const float4 s0 = *reinterpret_cast<const float4*>(P + L_ATT_SRC + 4 * p);
-    const float4 s1 = *reinterpret_cast<const float4*>(P + L_ATT_SRC + 16 + 4 * p);
-    const float4 d0 = *reinterpret_cast<const float4*>(P + L_ATT_DST + 4 * p);
-    const float4 d1 = *reinterpret_cast<const float4*>(P + L_ATT_DST + 16 + 4 * p);
-    const float as[2][4] = {{s0.x, s0.y, s0.z, s0.w}, {s1.x, s1.y, s1.z, s1.w}};
-    const float ad[2][4] = {{d0.x, d0.y, d0.z, d0.w}, {d1.x, d1.y, d1.z, d1.w}};
-    float ao[2][NS / 4];
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int ks = 0; ks < NS / 4; ++ks) ao[t][ks] = TB.dO[row0 + 4 * ks + p][16 * t + c];
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct) {
-      const int u = 16 * ct + c, uu = min(u, NS - 1);
-      float da_s = 0.0f;
-      if (conv == SWARM_CONV_GAT) {   // sum over the targets v of u's own graph
-        const int base = (GS < NS) ? (uu / GS) * GS : 0;
-        float dpj[GS];   // read unconditionally (rows of this wave's graph), summed for j < N
-#pragma unroll
-        for (int j = 0; j < GS; ++j) dpj[j] = TB.dp[row0 + base + j][uu];
-#pragma unroll
-        for (int j = 0; j < GS; ++j) asm volatile("" : "+v"(dpj[j]));
-#pragma unroll
-        for (int j = 0; j < GS; ++j) da_s = j < N ? da_s + dpj[j] : da_s;
-      }
-      const float das = nv[ct] ? da_s : 0.0f, dad = nv[ct] ? da_d[ct] : 0.0f;
-      f32x4 m0 = {0.f, 0.f, 0.f, 0.f}, m1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < NS / 4; ++ks) {
-        const float b = TB.cm[row0 + 4 * ks + p][uu];
-        m0 = mfma16(ao[0][ks], b, m0);
-        m1 = mfma16(ao[1][ks], b, m1);
-      }
-      float dh[2][4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        dh[0][r] = nv[ct] ? (m0[r] + das * as[0][r]) + dad * ad[0][r] : 0.0f;
-        dh[1][r] = nv[ct] ? (m1[r] + das * as[1][r]) + dad * ad[1][r] : 0.0f;
-      }
-      if (u < NS) {
-        *reinterpret_cast<float4*>(&TB.dH[row0 + u][4 * p]) = make_float4(dh[0][0], dh[0][1], dh[0][2], dh[0][3]);
-        *reinterpret_cast<float4*>(&TB.dH[row0 + u][16 + 4 * p]) = make_float4(dh[1][0], dh[1][1], dh[1][2], dh[1][3]);
-        if (p == 0) { TB.das[row0 + u] = das; TB.dad[row0 + u] = dad; }
-      }
-    }
+    bwd_dh<NS, GS>(TB, P, row0, N, conv, nv, da_d, c, p);
     SWARM_STAMP(27);
   } else {
     // ---- target waves: the dW1 / dW2 tiles of column half tj = wi (GPB = 2) or both (GPB = 1);
@@ -871,40 +623,15 @@ __device__ __forceinline__ void td_body(TdSmem<NS>& L, const int vb, const int32
     const int wall = online ? wi : GPB + wi;
     for (int job = wall; job < 4; job += 2 * GPB) {
       if (job < 2) {
-        const int t = job;
-        // operands read up front and unconditionally (column 8 of X is +0: the padding columns
-        // c >= kFeat read it), so no LDS round trip sits between two MFMAs of the chain
-        float ha[kTdRows / 4], xb[kTdRows / 4];
-#pragma unroll
-        for (int ks = 0; ks < kTdRows / 4; ++ks) {
-          const int n = 4 * ks + p;
-          ha[ks] = TB.dH[n][16 * t + c];
-          xb[ks] = TB.X[n][c < kFeat ? c : 8];
-        }
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ks = 0; ks < kTdRows / 4; ++ks) acc = mfma16(ha[ks], xb[ks], acc);
+        const f32x4 acc = bwd_dw_tile(TB, job, c, p);
         if (c < kFeat) {
 #pragma unroll
-          for (int r = 0; r < 4; ++r) sst(OFF_W + (16 * t + 4 * p + r) * kFeat + c, acc[r]);
+          for (int r = 0; r < 4; ++r) sst(OFF_W + (16 * job + 4 * p + r) * kFeat + c, acc[r]);
         }
-      } else if (job == 2) {   // att_src (half 0) / att_dst (half 1): sum_n da[n] H[n][col]
-        const float* da = h == 0 ? TB.das : TB.dad;
-        float v[kTdRows];
-#pragma unroll
-        for (int n = 0; n < kTdRows; ++n) v[n] = da[n] * TB.H[n][col];
-        float acc = v[0];
-#pragma unroll
-        for (int n = 1; n < kTdRows; ++n) acc = acc + v[n];
-        sst((h == 0 ? OFF_ATT_SRC : OFF_ATT_DST) + col, acc);
+      } else if (job == 2) {   // att_src (half 0) / att_dst (half 1)
+        sst((h == 0 ? OFF_ATT_SRC : OFF_ATT_DST) + col, bwd_att_col(TB, h == 0 ? TB.das : TB.dad, col));
       } else if (lane < kHidden) {
-        float v[kTdRows];
-#pragma unroll
-        for (int n = 0; n < kTdRows; ++n) v[n] = TB.dO[n][lane];
-        float acc = v[0];
-#pragma unroll
-        for (int n = 1; n < kTdRows; ++n) acc = acc + v[n];
-        sst(OFF_BIAS + lane, acc);
+        sst(OFF_BIAS + lane, col_sum32(TB.dO, lane));
       }
     }
   }

@@ -7,8 +7,10 @@ two objects are compared by names and bytes only (no instruction is inspected):
   - per symbol, its code bytes (address and size into .text; its position may differ, so the
     4-byte fields the linker relocated, a call's pc-relative offset to another function, are
     compared as (offset in the symbol, relocation type, target) instead of as bytes);
-  - per kernel, its metadata note: VGPR / SGPR / AGPR counts, LDS, scratch and kernarg sizes.
-A host-side refactor must leave all three equal: the kernels cannot tell who launched them.
+  - per kernel, its metadata note: VGPR / SGPR / AGPR counts, LDS, scratch and kernarg sizes;
+  - per kernel, the occupancy (waves per SIMD) of the compiler's kernel-resource-usage remarks.
+A host-side refactor must leave all of them equal: the kernels cannot tell who launched them.  A
+kernel refactor may move code bytes and register counts; its LDS, scratch, kernarg and occupancy stay.
 
 usage: python tools/codeobj_diff.py TREE_A TREE_B [--extra=-DSWARM_STAMPS=1 ...] [--keep DIR]
 Translation units that only one tree has are named and left out of the comparison.
@@ -37,10 +39,19 @@ def tool(name, *args):
 
 
 def compile_start(tree, src, extra, out):
+    """the compiler's own resource remarks (registers, occupancy) of the unit go to out + '.remarks'"""
     csrc = glob.glob(os.path.join(tree, "*", "csrc"))[0]
     flags = [f for f in B.FLAGS if f != "-shared"]
-    return subprocess.Popen([B.HIPCC, *flags, '-DSWARM_SRC_DIGEST="codeobj_diff"', *extra, "--cuda-device-only", "-c",
-                             "-Xoffload-linker", "--emit-relocs", "-o", out, os.path.join(csrc, src)])
+    with open(out + ".remarks", "w") as err:
+        return subprocess.Popen([B.HIPCC, *flags, '-DSWARM_SRC_DIGEST="codeobj_diff"', *extra, "--cuda-device-only", "-c",
+                                 "-Rpass-analysis=kernel-resource-usage", "-Xoffload-linker", "--emit-relocs", "-o", out,
+                                 os.path.join(csrc, src)], stderr=err)
+
+
+def occupancy(obj):
+    """{kernel: waves per SIMD} as the compiler printed them for obj"""
+    text = open(obj + ".remarks").read()
+    return dict(re.findall(r"Function Name: (\S+).*\n(?:.*\n)*?.*Occupancy \[waves/SIMD\]: (\d+)", text))
 
 
 def describe(obj):
@@ -114,19 +125,25 @@ def main():
         code = [n for n in names if da[n][:2] != db[n][:2]]
         note = [n for n in names if da[n][2] != db[n][2]]
         kernels = sum(1 for n in names if da[n][2] is not None)
-        ok = sorted(da) == sorted(db) and not code and not note
+        oa, ob = occupancy(objs["a", s]), occupancy(objs["b", s])
+        occ = [n for n in names if oa.get(n) != ob.get(n)]
+        ok = sorted(da) == sorted(db) and not code and not note and not occ
         same = same and ok
         print(f"{s}: {len(da)} / {len(db)} .text functions ({kernels} kernels with a metadata note), symbol lists "
               f"{'identical' if sorted(da) == sorted(db) else 'DIFFER'}, code bytes "
-              f"{'identical' if not code else 'DIFFER'}, kernel metadata {'identical' if not note else 'DIFFER'}")
+              f"{'identical' if not code else 'DIFFER'}, kernel metadata {'identical' if not note else 'DIFFER'}, "
+              f"occupancy {'identical' if not occ else 'DIFFER'}")
         for n in sorted(set(da) ^ set(db)):
             print(f"  only in {'A' if n in da else 'B'}: {n}")
         for n in code:
             print(f"  code differs: {n} ({len(da[n][0])} / {len(db[n][0])} bytes)")
         for n in note:
             print(f"  metadata differs: {n}: {da[n][2]} / {db[n][2]}")
-        for n in names:   # size, relocated fields, the note in NOTE_KEYS order
-            print(f"  = {len(da[n][0]):7d} B {len(da[n][1]):2d} rel  {da[n][2] and ' '.join(da[n][2][k] for k in NOTE_KEYS)}  {n}")
+        for n in occ:
+            print(f"  occupancy differs: {n}: {oa.get(n)} / {ob.get(n)} waves per SIMD")
+        for n in names:   # tree A: size, relocated fields, the note in NOTE_KEYS order, waves per SIMD
+            print(f"  = {len(da[n][0]):7d} B {len(da[n][1]):2d} rel  {da[n][2] and ' '.join(da[n][2][k] for k in NOTE_KEYS)}"
+                  f"  occ {oa.get(n)}  {n}")
     print("IDENTICAL" if same else "DIFFERENT")
     return 0 if same else 1
 
