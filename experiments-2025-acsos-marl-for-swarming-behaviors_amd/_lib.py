@@ -131,6 +131,11 @@ _PROTOS = {
     "swarm_pop_train_tick": (c_int32, [POINTER(SwarmConfig), POINTER(SwarmAdamCfg), c_void_p, c_int32, c_stream]),
     "swarm_pop_reduce_advance": (c_int32, [POINTER(SwarmConfig), POINTER(SwarmAdamCfg), c_void_p, c_int32,
                                            c_stream]),
+    # (cfg, shared hp, member_hp table [P] of SwarmAdamCfg in device memory, members table, P, stream)
+    "swarm_pop_train_tick_hp": (c_int32, [POINTER(SwarmConfig), POINTER(SwarmAdamCfg), c_void_p, c_void_p, c_int32,
+                                          c_stream]),
+    "swarm_pop_reduce_advance_hp": (c_int32, [POINTER(SwarmConfig), POINTER(SwarmAdamCfg), c_void_p, c_void_p,
+                                              c_int32, c_stream]),
     "swarm_peer_buffer_bytes": (c_int64, []),
     "swarm_peer_alloc": (c_int32, [POINTER(c_void_p)]),
     "swarm_peer_free": (c_int32, [c_void_p]),

@@ -198,7 +198,12 @@ class PopulationTrainer:
 
     ``train_model(config)`` runs the loop of ``DQNTrainer.train_model`` for all trainers at once and
     leaves each trainer as its own ``train_model`` would: the same episode lists and writer scalars,
-    the same ``.pth`` and ``.csv`` files (members compute a lone engine's bits)."""
+    the same ``.pth`` and ``.csv`` files (members compute a lone engine's bits).
+
+    The trainers may differ in ``lr``, ``gamma`` and ``update_target_every`` (a sweep: the population
+    then ticks with one optimizer row per member), and ``config``'s ``epsilon``, ``epsilon_decay`` and
+    ``min_epsilon`` may each be a sequence of one value per trainer; they share ``batch_size``, the
+    ring capacity and everything else of the configuration."""
 
     def __init__(self, trainers):
         self.trainers = list(trainers)
@@ -236,6 +241,10 @@ class PopulationTrainer:
                     "Models saved successfully!")
 
 
+def _is_sequence(v) -> bool:
+    return isinstance(v, (list, tuple)) or hasattr(v, "tolist") and getattr(v, "ndim", 0) > 0
+
+
 def _train_loop(driver, group, trainers, shape, config, prefix: str, saved: str):
     """The reference's episode loop (train_gcn_dqn.py:139-204) for ``trainers`` ticked together by
     ``group`` (a SwarmEngine with its one trainer, or a SwarmPopulation): reset / set_eps / capture.
@@ -243,9 +252,15 @@ def _train_loop(driver, group, trainers, shape, config, prefix: str, saved: str)
     (``_episode_fn``, on per-episode buffers of ``shape``, per-tick ones of [max_steps, *shape]: () for
     a lone engine, (P,) for a population) and the end-of-episode checks (``_check_episode``)."""
     first, P = trainers[0], len(trainers)
-    initial_epsilon = config["epsilon"]
-    epsilon_decay = config["epsilon_decay"]
-    min_epsilon = config["min_epsilon"]
+    # with a population each of the three may be one value per member: the same schedule, evaluated
+    # per member (a lone trainer's, with scalars, is unchanged)
+    schedule = [config["epsilon"], config["epsilon_decay"], config["min_epsilon"]]
+    per_member_eps = shape != () and any(_is_sequence(v) for v in schedule)
+    if per_member_eps:
+        schedule = [list(v) if _is_sequence(v) else [v] * P for v in schedule]
+        if any(len(v) != P for v in schedule):
+            raise ValueError(f"epsilon, epsilon_decay and min_epsilon: scalars or {P} values each")
+    initial_epsilon, epsilon_decay, min_epsilon = schedule
     episodes = config["episodes"]
     max_steps = first.env.max_steps or 100
     epsilon = initial_epsilon
@@ -269,7 +284,10 @@ def _train_loop(driver, group, trainers, shape, config, prefix: str, saved: str)
         else:
             for _ in range(max_steps):
                 tick_fn()
-        epsilon = max(min_epsilon, initial_epsilon * np.exp(-epsilon_decay * episode))
+        if per_member_eps:
+            epsilon = [max(lo, e0 * np.exp(-d * episode)) for e0, d, lo in zip(*schedule)]
+        else:
+            epsilon = max(min_epsilon, initial_epsilon * np.exp(-epsilon_decay * episode))
         # the episode's scalars of every member, read once: the sums [P], the per-tick ones [max_steps][P]
         acc_loss, acc_reward = driver._acc_loss.reshape(P).tolist(), driver._acc_reward.reshape(P).tolist()
         rew_t, loss_t, tr_t = (x.reshape(max_steps, P).tolist()
@@ -289,7 +307,7 @@ def _train_loop(driver, group, trainers, shape, config, prefix: str, saved: str)
                 t.episode_rewards.append(sum(t.rewards_buffer) / 10)
                 t.rewards_buffer = []
             print(f"{prefix.format(seed=t.seed)}Episode {episode}, Loss: {average_loss}, "
-                  f"Reward: {ep_reward * t.env.n_agents}, Epsilon: {epsilon}")
+                  f"Reward: {ep_reward * t.env.n_agents}, Epsilon: {epsilon[m] if per_member_eps else epsilon}")
         ticks += max_steps
     print("Training completed")
     for t in trainers:

@@ -33,6 +33,7 @@ once into a hipGraph (``capture``) and replayed.  There is no CPU fallback.
 from __future__ import annotations
 
 import math
+import numbers
 from typing import Optional
 
 import torch
@@ -204,6 +205,23 @@ class SwarmEngine:
     # ------------------------------------------------------------------ control block
     def set_eps(self, eps: float):
         self.ctrl.view(torch.float32)[CTRL["eps"]].fill_(float(eps))
+
+    def set_hp(self, **fields):
+        """Change optimizer hyper-parameters (``HP_FIELDS``: lr, gamma, betas, adam_eps, max_norm,
+        update_target_every) for the launches that follow.  ``hp`` is a kernel argument of every
+        launch, so eager calls see the new values at once and a hipGraph captured before keeps
+        the old ones.  The control block holds the next optimizer step's Adam scalars, formed
+        from the hp of the launch that wrote them: a new lr (or beta) acts one optimizer step
+        later.  ``SwarmPopulation.set_member_hp`` is defined by this method."""
+        check_hp_values(**fields)
+        hp = self.hp
+        for k, v in fields.items():
+            if k == "lr":
+                hp.lr, hp.lr_d = v, float(v)
+            elif k == "betas":
+                hp.beta1, hp.beta2, hp.beta1_d, hp.beta2_d = v[0], v[1], float(v[0]), float(v[1])
+            else:
+                setattr(hp, {"adam_eps": "eps"}.get(k, k), v)
 
     def read_ctrl(self) -> dict:
         return decode_ctrl(self.ctrl.cpu())
@@ -385,6 +403,34 @@ class SwarmEngine:
     def load_state_dict(self, sd):
         self.params.copy_(flatten_state_dict(sd, net=self.net).to(self.device))
         self.target.copy_(self.params)
+
+
+# the optimizer hyper-parameters a learner can change after it is built (SwarmEngine.set_hp) and a
+# population can hold per member (SwarmPopulation): SwarmEngine's keyword names
+HP_FIELDS = ("lr", "gamma", "betas", "adam_eps", "max_norm", "update_target_every")
+
+
+def check_hp_values(**fields):
+    """Raise ValueError unless every given HP_FIELDS value is one the kernels can run with: finite,
+    lr >= 0, adam_eps >= 0, betas a pair in [0, 1) (torch.optim.Adam's own checks), max_norm >= 0
+    and update_target_every an integer >= 1 (the kernels take a tick count modulo it)."""
+    for k, v in fields.items():
+        if k not in HP_FIELDS:
+            raise ValueError(f"{k!r} is not an optimizer hyper-parameter ({', '.join(HP_FIELDS)})")
+        if k == "betas":
+            if not (isinstance(v, (tuple, list)) and len(v) == 2 and all(_is_number(b) for b in v)):
+                raise ValueError(f"betas must be a pair of numbers, not {v!r}")
+            if not all(math.isfinite(b) and 0.0 <= b < 1.0 for b in v):
+                raise ValueError(f"betas must lie in [0, 1): {v!r}")
+        elif k == "update_target_every":
+            if isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < 1:
+                raise ValueError(f"update_target_every must be an integer >= 1, not {v!r}")
+        elif not _is_number(v) or not math.isfinite(v) or (k != "gamma" and v < 0):
+            raise ValueError(f"{k} must be a finite number{'' if k == 'gamma' else ' >= 0'}, not {v!r}")
+
+
+def _is_number(v) -> bool:
+    return isinstance(v, numbers.Real) and not isinstance(v, bool)
 
 
 def norm_flags(exact: bool) -> int:

@@ -8,9 +8,12 @@ block and a few TD blocks, about 1 % of the chip, so the seeds can share the tic
                               fused tick                                              (1 launch)
     swarm_pop_reduce_advance  grid (109, P): member m's slab sum, copy-back, ctrl     (1 launch)
 
-All members share one configuration except the seed, and one set of optimizer
-hyper-parameters.  Each member is an ordinary ``SwarmEngine`` (``pop.members[m]``: ``state_dict``,
-``read_ctrl``, ``rollout``, ``flush`` ... work per member) that owns its state, replay ring,
+All members share one configuration except the seed.  The optimizer's hyper-parameters (lr,
+gamma, betas, adam_eps, max_norm, update_target_every) may be one value for all or one per
+member: a sweep runs in the same two launches (swarm_pop_train_tick_hp /
+swarm_pop_reduce_advance_hp read member m's row of a device table; ``per_member_hp``).  Each
+member is an ordinary ``SwarmEngine`` (``pop.members[m]``: ``state_dict``, ``read_ctrl``,
+``rollout``, ``flush`` ... work per member) that owns its state, replay ring,
 learner, control block, slabs, hand-off workspace, samples and outputs; the population only moves
 every member's control block, reward, avg_dist, hits and hand-off workspace into rows of
 contiguous ``[P, ...]`` tensors, so the per-tick bookkeeping of a trainer is a fixed number of
@@ -25,7 +28,7 @@ from typing import Sequence
 import torch
 
 from ._lib import CTRL, SwarmAdamCfg, SwarmConfig, SwarmPopMember, call, ptr
-from .engine import SwarmEngine, capture_ticks, decode_ctrl, norm_flags
+from .engine import HP_FIELDS, SwarmEngine, capture_ticks, check_hp_values, decode_ctrl, norm_flags
 
 
 def _bytes_of(struct) -> bytes:
@@ -36,9 +39,39 @@ def _copy_of(struct):
     return type(struct).from_buffer_copy(_bytes_of(struct))
 
 
+def _is_pair(v) -> bool:
+    return isinstance(v, (tuple, list)) and len(v) == 2 and not any(hasattr(b, "__len__") for b in v)
+
+
+def member_hp_kwargs(P: int, engine_kwargs: dict) -> list:
+    """Split SwarmPopulation's keyword arguments into one dict per member, with nothing built: each
+    of lr, gamma, adam_eps, max_norm and update_target_every is one value for all members or a
+    sequence of P values; betas is the shared pair (a bare 2-sequence of numbers always is) or a
+    sequence of P pairs.  Raises ValueError for a sequence of another length and for a value
+    ``check_hp_values`` refuses (update_target_every < 1, a non-finite number ...)."""
+    per_member = [dict(engine_kwargs) for _ in range(P)]
+    for k in HP_FIELDS:
+        if k not in engine_kwargs:
+            continue
+        v = engine_kwargs[k]
+        if hasattr(v, "tolist"):   # a numpy array or a tensor of values
+            v = v.tolist()
+        seq = isinstance(v, (tuple, list)) and not (k == "betas" and _is_pair(v))
+        if seq and len(v) != P:
+            raise ValueError(f"{k}: {len(v)} values for {P} members")
+        for m, kw in enumerate(per_member):
+            kw[k] = v[m] if seq else v
+            if k == "betas" and isinstance(kw[k], list):
+                kw[k] = tuple(kw[k])
+            check_hp_values(**{k: kw[k]})
+    return per_member
+
+
 class SwarmPopulation:
     def __init__(self, seeds: Sequence[int], **engine_kwargs):
-        """``seeds`` plus the keyword arguments of ``SwarmEngine`` (everything but ``seed``)."""
+        """``seeds`` plus the keyword arguments of ``SwarmEngine`` (everything but ``seed``); the
+        optimizer's (``engine.HP_FIELDS``) may each be a sequence of one value per member
+        (``member_hp_kwargs``)."""
         seeds = list(seeds)
         if not seeds:
             raise ValueError("a population needs at least one seed")
@@ -48,12 +81,14 @@ class SwarmPopulation:
             raise ValueError("a population is made of learners: learn=False has nothing to tick together")
         if engine_kwargs.get("world_size", 1) > 1 or engine_kwargs.get("peer") is not None:
             raise ValueError("a population runs on one GPU: no world_size > 1, no peer exchange")
-        self._adopt([SwarmEngine(seed=s, **engine_kwargs) for s in seeds])
+        per_member = member_hp_kwargs(len(seeds), engine_kwargs)
+        self._adopt([SwarmEngine(seed=s, **kw) for s, kw in zip(seeds, per_member)])
 
     @classmethod
     def from_engines(cls, engines: Sequence[SwarmEngine]) -> "SwarmPopulation":
         """A population of engines that exist already (PopulationTrainer re-homes its trainers'
-        engines this way).  They must agree in everything but the seed."""
+        engines this way).  They must agree in everything but the seed and the optimizer's
+        per-member hyper-parameters: one configuration, batch, ring capacity and device."""
         self = cls.__new__(cls)
         self._adopt(list(engines))
         return self
@@ -66,12 +101,10 @@ class SwarmPopulation:
         self.lib = first.lib
         self.device = first.device
 
-        def shared(e):   # what every member must share: the configuration without the seed, the optimizer
-            c = _copy_of(e.cfg)
+        def shared(e):   # what every member must share: the configuration without the seed, and what
+            c = _copy_of(e.cfg)   # of the optimizer fixes the launch (batch: grid, S, loss scale, slabs)
             c.seed = 0
-            h = _copy_of(e.hp)
-            h.flags = 0
-            return _bytes_of(c), _bytes_of(h), e.capacity, e.device
+            return _bytes_of(c), e.hp.batch, e.hp.world_size, e.capacity, e.device
         for e in members:
             if e.world_size > 1 or e.peer is not None:
                 raise ValueError("a population runs on one GPU: no world_size > 1, no peer exchange")
@@ -79,14 +112,16 @@ class SwarmPopulation:
                 raise ValueError("a population needs a configuration the fused training tick covers "
                                  "(a learner, n_agents <= 16, net='gcn', a complete, kNN or radius graph)")
             if shared(e) != shared(first):
-                raise ValueError("the members of a population share one configuration (all but the seed) and one "
-                                 "set of optimizer hyper-parameters")
+                raise ValueError("the members of a population share one configuration (all but the seed), one "
+                                 "batch size and one ring capacity")
         if len({id(e) for e in members}) != len(members):
             raise ValueError("an engine can be a member only once")
         self.members = members
         self.P = P = len(members)
         self.B, self.N = first.B, first.N
         self.cfg: SwarmConfig = _copy_of(first.cfg)      # cfg.seed is not used: each member's own is
+        # the shared hp: batch, world_size and the launch's flags for every member; its other
+        # fields are the optimizer of every member while per_member_hp is False
         self.hp: SwarmAdamCfg = _copy_of(first.hp)
         dev = self.device
         f32 = dict(dtype=torch.float32, device=dev)
@@ -106,6 +141,20 @@ class SwarmPopulation:
         # the descriptor tables in device memory, written once: one per output set of train_tick
         self._table_full = self._table(lambda e: e.out)
         self._table_min = self._table(lambda e: e.out_min)
+        # every member's optimizer row (its engine's hp) in device memory, read by the _hp entry
+        # points on every launch; rewritten by set_member_hp
+        rows = (SwarmAdamCfg * P)(*[self._row(e) for e in members])
+        self._hp_table = torch.frombuffer(bytearray(_bytes_of(rows)), dtype=torch.uint8).to(dev).view(P, -1)
+        self.per_member_hp = self._rows_differ()
+
+    @staticmethod
+    def _row(e) -> SwarmAdamCfg:
+        r = _copy_of(e.hp)
+        r.flags = 0   # a row's batch, world_size and flags are ignored; flags change per launch
+        return r
+
+    def _rows_differ(self) -> bool:
+        return len({_bytes_of(self._row(e)) for e in self.members}) > 1
 
     def _table(self, out_of) -> torch.Tensor:
         arr = (SwarmPopMember * self.P)()
@@ -118,16 +167,43 @@ class SwarmPopulation:
     # ------------------------------------------------------------------ the tick
     def train_tick(self, full_out: bool = False):
         """One fused training tick of every member: two launches.  Each member's TD batch indices
-        go to its ``samples``; with full_out its Q, actions and obs are written too."""
+        go to its ``samples``; with full_out its Q, actions and obs are written too.
+
+        While ``per_member_hp`` is False (all rows equal) these are swarm_pop_train_tick and
+        swarm_pop_reduce_advance with the shared hp as a kernel argument; otherwise the _hp pair,
+        which reads each member's row of the device table."""
         # the reduce's clip-norm partials describe every member's grad unless one declared a write
         dirty = any(e._grad_dirty for e in self.members)
         self.hp.flags = norm_flags(not dirty)
         table = self._table_full if full_out else self._table_min
-        call(self.lib, "swarm_pop_train_tick", self.cfg, self.hp, ptr(table), self.P)
+        hp_table = (ptr(self._hp_table),) if self.per_member_hp else ()
+        sfx = "_hp" if self.per_member_hp else ""
+        call(self.lib, "swarm_pop_train_tick" + sfx, self.cfg, self.hp, *hp_table, ptr(table), self.P)
         if dirty:
             for e in self.members:
                 e._grad_dirty = False   # the reduce below rewrites grad and its partials
-        call(self.lib, "swarm_pop_reduce_advance", self.cfg, self.hp, ptr(table), self.P)
+        call(self.lib, "swarm_pop_reduce_advance" + sfx, self.cfg, self.hp, *hp_table, ptr(table), self.P)
+
+    def set_member_hp(self, m: int, **fields):
+        """Change member m's optimizer hyper-parameters (``engine.HP_FIELDS``) for the ticks that
+        follow: ``members[m].set_hp(**fields)`` (so the member's own ``flush`` agrees) plus row m of
+        the device table, and ``per_member_hp`` becomes True if the rows now differ.  It means what
+        ``SwarmEngine.set_hp`` between two eager ticks means for a lone engine, bit for bit (a new
+        lr acts one optimizer step later, see there).  The table is read on every launch, so a
+        hipGraph captured while ``per_member_hp`` was True sees the new row at its next replay; one
+        captured while it was False holds the shared hp as a kernel argument and does not (set
+        ``per_member_hp = True`` before capturing a population whose rows will change)."""
+        if not 0 <= m < self.P:
+            raise ValueError(f"member {m} of {self.P}")
+        e = self.members[m]
+        e.set_hp(**fields)   # validates
+        row = torch.frombuffer(bytearray(_bytes_of(self._row(e))), dtype=torch.uint8)
+        self._hp_table[m].copy_(row)   # on the current stream: behind every tick issued so far
+        if m == 0:   # the shared hp follows member 0, as at adoption (all there is when the rows are equal)
+            flags = self.hp.flags
+            self.hp = _copy_of(e.hp)
+            self.hp.flags = flags
+        self.per_member_hp = self.per_member_hp or self._rows_differ()
 
     def reset(self, episode=None):
         """Reset every member's environments (one small launch per member, once per episode)."""

@@ -308,6 +308,32 @@ int swarm_pop_train_tick(const swarm_config* cfg, const swarm_adam_cfg* hp, cons
 int swarm_pop_reduce_advance(const swarm_config* cfg, const swarm_adam_cfg* hp, const swarm_pop_member* members,
                              int32_t n_members, void* stream);
 
+/* The same two launches with the optimizer's hyper-parameters PER MEMBER: a learning-rate, gamma,
+ * clip, Adam or target-sync sweep run as one population (the reference fixes them for all seeds,
+ * train_gcn_dqn.py:85,112-137,175, and runs once per seed, :262-290; a sweep is that loop again
+ * per setting).  member_hp is an array of n_members swarm_adam_cfg in DEVICE memory; like
+ * `members` it is written by the caller and read by the kernels on every launch, so a row
+ * rewritten between two launches holds from the next launch on, the next replay of a captured
+ * hipGraph included (a kernel-argument hp is frozen into the graph).
+ *   per member, from row m : lr, beta1, beta2, eps, max_norm, gamma, update_target_every,
+ *                            lr_d, beta1_d, beta2_d;
+ *   shared, from *hp       : batch, world_size (= 1) and flags.  batch fixes the grid, the TD
+ *                            batch size, the loss scale and the slab count, which a launch has
+ *                            once.  These three fields of the rows are IGNORED.
+ * Checks: those of swarm_pop_train_tick on cfg, hp, members and n_members, in the same order
+ * (hp's own update_target_every >= 1 among them, though the rows' values are what the kernels
+ * use); member_hp == NULL returns SWARM_E_BADARG, as members == NULL does.  The entry points
+ * cannot look into device memory: every row must hold update_target_every >= 1 and finite values
+ * (lr >= 0, eps >= 0, betas in [0, 1) as torch.optim.Adam asks, max_norm >= 0): that is the
+ * caller's contract (SwarmPopulation enforces it).  Each member's control block comes from
+ * swarm_ctrl_init with its own row, and its swarm_adam_flush takes its own row.  With all rows
+ * equal to *hp both calls compute the bits of swarm_pop_train_tick / swarm_pop_reduce_advance
+ * (tests/test_gpu_population_hp.py). */
+int swarm_pop_train_tick_hp(const swarm_config* cfg, const swarm_adam_cfg* hp, const swarm_adam_cfg* member_hp,
+                            const swarm_pop_member* members, int32_t n_members, void* stream);
+int swarm_pop_reduce_advance_hp(const swarm_config* cfg, const swarm_adam_cfg* hp, const swarm_adam_cfg* member_hp,
+                                const swarm_pop_member* members, int32_t n_members, void* stream);
+
 /* ---- Peer all-reduce over xGMI (the one exchange of the data-parallel tick).
  * The reference has no distributed code; this replaces the RCCL all_reduce(grad) that would
  * follow swarm_reduce_advance (dist.py allreduce_grad_).  Every rank owns one exchange buffer

@@ -4,10 +4,12 @@ At the reference's shape (src/training/train_gcn_dqn.py:262-290: 1 env, batch 32
 ring, 100-tick episodes) and P learners (seeds 0..P-1), two ways of running one episode of all P:
   sequential : P lone SwarmEngines, each replaying its own captured 100-tick episode (hipGraph),
                one after another on one stream: what running the seeds in turn costs;
-  population : one SwarmPopulation replaying one captured 100-tick episode of all P members.
-Both are timed between two HIP events around `K` back-to-back episode replays (no host
-synchronisation inside), after a warm-up of both that also fills the replay rings past the batch
-size, so every timed tick trains.  The two alternate, `--repeats` times each; the table gives the
+  population : one SwarmPopulation replaying one captured 100-tick episode of all P members;
+  population_hp : the same with one optimizer row per member (swarm_pop_train_tick_hp /
+               swarm_pop_reduce_advance_hp): the members get distinct lr and gamma values.
+All are timed between two HIP events around `K` back-to-back episode replays (no host
+synchronisation inside), after a warm-up of all that also fills the replay rings past the batch
+size, so every timed tick trains.  The ways alternate, `--repeats` times each; the table gives the
 median and the spread in us per population tick (= one tick of all P learners).  Environment
 resets are not timed (they are per-member launches in both).
 
@@ -45,19 +47,26 @@ def measure(scen, N, P, repeats):
     kw = dict(scenario=scen, n_agents=N, n_envs=1, batch=32, eps=0.05, shared_reset=True)
     lone = [swarm_amd.SwarmEngine(seed=s, **kw) for s in range(P)]
     pop = swarm_amd.SwarmPopulation(seeds=list(range(P)), **kw)
+    # a sweep: every member its own lr and gamma; P = 1 has one row, so the _hp pair is forced
+    sweep = dict(lr=[1e-3 / (1 + m / 8) for m in range(P)], gamma=[0.99 - 0.25 * m / P for m in range(P)])
+    pop_hp = swarm_amd.SwarmPopulation(seeds=list(range(P)), **sweep, **kw)
+    pop_hp.per_member_hp = True
+    assert not pop.per_member_hp
     for e in lone:
         e.reset(0)
     pop.reset(0)
+    pop_hp.reset(0)
     lone_graphs = [e.capture(TICKS) for e in lone]
     pop_graph = pop.capture(TICKS)
+    pop_hp_graph = pop_hp.capture(TICKS)
 
     def sequential():
         for g in lone_graphs:
             g.replay()
 
-    ways = {"sequential": sequential, "population": pop_graph.replay}
+    ways = {"sequential": sequential, "population": pop_graph.replay, "population_hp": pop_hp_graph.replay}
     # enough episodes per window that it lasts tens of milliseconds at least
-    episodes = {"sequential": max(2, math.ceil(40 / P)), "population": 40}
+    episodes = {"sequential": max(2, math.ceil(40 / P)), "population": 40, "population_hp": 40}
     for k, fn in ways.items():   # warm-up: code objects loaded, rings past the batch size, clocks up
         window_us(fn, 2)
     times = {k: [] for k in ways}
@@ -66,9 +75,10 @@ def measure(scen, N, P, repeats):
             times[k].append(window_us(fn, episodes[k]))
     torch.cuda.synchronize()
     pop.check_handoffs()
+    pop_hp.check_handoffs()
     for e in lone:
         e.check_handoffs()
-    steps = [c["adam_step"] for c in pop.read_ctrl()]
+    steps = [c["adam_step"] for c in pop.read_ctrl() + pop_hp.read_ctrl()]
     assert min(steps) > 0, "the timed ticks did not train"
     out = {"scenario": scen, "n_agents": N, "n_envs": 1, "batch": 32, "population": P, "ticks_per_episode": TICKS,
            "episodes_per_window": episodes, "repeats": repeats, "build": pop.lib.swarm_build_info().decode()}
@@ -76,6 +86,7 @@ def measure(scen, N, P, repeats):
         out[k + "_us_per_tick"] = round(statistics.median(v), 3)
         out[k + "_us_min_max"] = [round(min(v), 3), round(max(v), 3)]
     out["sequential_over_population"] = round(out["sequential_us_per_tick"] / out["population_us_per_tick"], 3)
+    out["population_hp_over_population"] = round(out["population_hp_us_per_tick"] / out["population_us_per_tick"], 4)
     return out
 
 

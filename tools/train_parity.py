@@ -16,10 +16,14 @@ the N the recorded runs used.  ``--agents`` sweeps it.
 
     python tools/train_parity.py [--out out.json] [--seeds 0,1,...] [--episodes 1000]
                                  [--scenarios GoTo,ObstacleAvoidance] [--agents 10[,5,...]]
-                                 [--population]
+                                 [--population [--lr 1e-3,3e-4,... --gamma 0.99,0.95,...]]
 
 ``--population`` trains the seeds of a scenario and agent count together (PopulationTrainer: one
 launch ticks every seed) instead of one after another; the curves are the same bits.
+``--lr`` / ``--gamma`` (with ``--population``) give the members their own learning rate / discount:
+one value for all, or one per seed in the order of ``--seeds``.  That is a sweep in one run; each
+member's setting is recorded with its curve (``member_hp``), and the comparison with the
+reference's recorded curves then describes the sweep, not the reference's configuration.
 """
 import argparse
 import contextlib
@@ -49,8 +53,8 @@ def run(scen_name, seed, episodes, n_agents=10):
     return [float(x) for x in tr.episode_rewards]
 
 
-def run_population(scen_name, seeds, episodes, n_agents=10):
-    """run() for all seeds at once: {seed: curve}"""
+def run_population(scen_name, seeds, episodes, n_agents=10, lr=None, gamma=None):
+    """run() for all seeds at once: {seed: curve}; lr / gamma: one value per seed, or None"""
     import swarm_amd
     with tempfile.TemporaryDirectory() as d:
         trainers = []
@@ -59,8 +63,9 @@ def run_population(scen_name, seeds, episodes, n_agents=10):
             env = swarm_amd.make_env(scenario=scen, num_envs=1, continuous_actions=False, wrapper=None, max_steps=100,
                                      dict_spaces=True, n_agents=n_agents, seed=seed)
             swarm_amd.set_seed(seed)
+            hp = {k: v[len(trainers)] for k, v in (("lr", lr), ("gamma", gamma)) if v is not None}
             trainers.append(swarm_amd.DQNTrainer(env, seed, os.path.join(d, "models"), os.path.join(d, "stats"),
-                                                 scen_name))
+                                                 scen_name, **hp))
         with contextlib.redirect_stdout(io.StringIO()):
             swarm_amd.PopulationTrainer(trainers).train_model(
                 {"epsilon": 0.99, "epsilon_decay": 0.01, "min_epsilon": 0.05, "episodes": episodes})
@@ -118,19 +123,32 @@ def main():
     ap.add_argument("--scenarios", default="GoTo,ObstacleAvoidance")
     ap.add_argument("--agents", default="10")
     ap.add_argument("--population", action="store_true", help="train the seeds together (PopulationTrainer)")
+    ap.add_argument("--lr", default=None, help="with --population: learning rate, one value or one per seed")
+    ap.add_argument("--gamma", default=None, help="with --population: discount, one value or one per seed")
     a = ap.parse_args()
     seeds = [int(s) for s in a.seeds.split(",")]
+    sweep = {}
+    for k in ("lr", "gamma"):
+        if getattr(a, k) is not None:
+            if not a.population:
+                ap.error(f"--{k} needs --population")
+            v = [float(x) for x in getattr(a, k).split(",")]
+            if len(v) not in (1, len(seeds)):
+                ap.error(f"--{k}: one value or {len(seeds)} (one per seed), not {len(v)}")
+            sweep[k] = v * len(seeds) if len(v) == 1 else v
     ref = json.load(open(os.path.join(ROOT, "tests", "golden", "train_stats.json")))
     res = {"config": ref["config"] | {"episodes": a.episodes}, "seeds": seeds, "runs": []}
     for scen in a.scenarios.split(","):
         for n in [int(x) for x in a.agents.split(",")]:
             t0 = time.time()
-            ours = (run_population(scen, seeds, a.episodes, n) if a.population
+            ours = (run_population(scen, seeds, a.episodes, n, **sweep) if a.population
                     else {s: run(scen, s, a.episodes, n) for s in seeds})
             secs = time.time() - t0
             r = compare(ref, scen, ours, seeds, a.episodes)
             r |= {"scenario": scen, "n_agents": n, "seconds": secs, "population": bool(a.population), "ticks": len(seeds) * a.episodes * 100,
                   "curves": {str(s): ours[s] for s in seeds}}
+            if sweep:
+                r["member_hp"] = {str(s): {k: v[i] for k, v in sweep.items()} for i, s in enumerate(seeds)}
             res["runs"].append(r)
             w = r.get("last100_welch", {})
             print(f"{scen:18s} N={n:2d} last-100 reward: ours {r['last100_mean'][0]:8.2f} +- {r['last100_std'][0]:.2f} "
