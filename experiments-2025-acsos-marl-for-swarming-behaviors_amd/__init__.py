@@ -7,6 +7,7 @@ this directory).  Public surface mirrors the reference:
     from swarm_amd import GCN, DQNTrainer, GraphReplayBuffer, Simulator, set_seed, get_scenario
     from swarm_amd import SwarmEngine          # the fused device engine underneath
     from swarm_amd import SwarmPopulation, PopulationTrainer   # many seeds in one launch
+    from swarm_amd import ActorPopulation, PopulationSimulator # many policies in one rollout launch
 
 The compute path is libswarm_hip.so (csrc/, C ABI in include/swarm_hip.h); there
 is no CPU fallback.
@@ -19,11 +20,11 @@ from .gcn import GCN  # noqa: F401
 from .scenarios import (BaseScenario, FlockingScenario, GoToPositionScenario, ObstacleAvoidanceScenario,  # noqa: F401
                         get_scenario)
 from .env import Environment, make_env  # noqa: F401
-from .population import SwarmPopulation  # noqa: F401
+from .population import ActorPopulation, SwarmPopulation  # noqa: F401
 from .dqn import DQNTrainer, GraphReplayBuffer, PopulationTrainer, set_seed  # noqa: F401
-from .simulator import Simulator  # noqa: F401
+from .simulator import PopulationSimulator, Simulator  # noqa: F401
 
-__all__ = ["SwarmEngine", "SwarmPopulation", "PopulationTrainer", "Data", "Batch", "GCN", "make_env", "Environment", "GoToPositionScenario",
+__all__ = ["SwarmEngine", "SwarmPopulation", "PopulationTrainer", "ActorPopulation", "PopulationSimulator", "Data", "Batch", "GCN", "make_env", "Environment", "GoToPositionScenario",
            "ObstacleAvoidanceScenario", "FlockingScenario", "BaseScenario", "get_scenario", "DQNTrainer", "GraphReplayBuffer",
            "set_seed", "Simulator", "create_graph_from_observations", "create_knn_graph_from_observations",
            "create_radius_graph_from_observations"]

@@ -67,6 +67,13 @@ class SwarmPopMember(ctypes.Structure):
                 ("sample_out", c_void_p)]
 
 
+class SwarmPopActor(ctypes.Structure):
+    """One actor of a population rollout (swarm_pop_actor): what swarm_rollout takes for a lone
+    policy.  The array of them lives in device memory (population.ActorPopulation)."""
+    _fields_ = [("seed", c_uint64), ("params", c_void_p), ("state", c_void_p), ("out", SwarmActOut),
+                ("tick0", c_uint32), ("eps", c_float)]
+
+
 PEER_MAX = 8
 PEER_HANDLE_BYTES = 64
 PEER_SEQ_WORDS = 256
@@ -136,6 +143,8 @@ _PROTOS = {
                                           c_stream]),
     "swarm_pop_reduce_advance_hp": (c_int32, [POINTER(SwarmConfig), POINTER(SwarmAdamCfg), c_void_p, c_void_p,
                                               c_int32, c_stream]),
+    # (cfg, actors table [P] of SwarmPopActor in device memory, P, n_ticks, stream)
+    "swarm_pop_rollout": (c_int32, [POINTER(SwarmConfig), c_void_p, c_int32, c_int32, c_stream]),
     "swarm_peer_buffer_bytes": (c_int64, []),
     "swarm_peer_alloc": (c_int32, [POINTER(c_void_p)]),
     "swarm_peer_free": (c_int32, [c_void_p]),

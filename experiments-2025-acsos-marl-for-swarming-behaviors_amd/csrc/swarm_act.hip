@@ -137,16 +137,10 @@ template <int MODE>
 int launch_act(const ActArgs& a, hipStream_t st) {
   if (a.B == 0) return 0;
   const dim3 grid((a.B + kActWPB - 1) / kActWPB), block(64 * kActWPB);
-  with_slots<8, 16, 32>(a.N, [&](auto ns) {
-    with_scenario<MODE != MODE_Q>(a.scenario, [&](auto sc) {
-      with_net<MODE != MODE_STEP>(a.net, [&](auto net) {
-        constexpr int NS = decltype(ns)::value, SC = decltype(sc)::value, NET = decltype(net)::value;
-        with_spec<ActSpecs<NS, MODE, SC, NET>>(a.graph, a.conv, [&](auto sp) {
-          hipLaunchKernelGGL((act_kernel<NS, MODE, SC, decltype(sp)::value, NET>), grid, block, 0, st, a.ctrl, a.state,
-                             a.lr.grad, a.lr.w_cur, a.lr.m_cur, a.lr.v_cur, a.B, a.N, a);
-        });
-      });
-    });
+  with_act_instance<MODE>(a, [&](auto ns, auto sc, auto net, auto sp) {
+    hipLaunchKernelGGL(
+        (act_kernel<decltype(ns)::value, MODE, decltype(sc)::value, decltype(sp)::value, decltype(net)::value>), grid,
+        block, 0, st, a.ctrl, a.state, a.lr.grad, a.lr.w_cur, a.lr.m_cur, a.lr.v_cur, a.B, a.N, a);
   });
   return (int)hipGetLastError();
 }

@@ -132,6 +132,20 @@ struct ActSpecs {
     return MODE == MODE_TICK && spec_complete(sp);
   }
 };
+// (N, scenario, net, graph, conv) -> f(NS, SCEN, NET, SPEC) of the act_kernel instance of MODE
+// (ActSpecs); launch_act (swarm_act.hip) and the population rollout (swarm_pop_rollout.hip), whose
+// kernel template takes <NS, SCEN, SPEC, NET> for MODE_ROLLOUT, name their kernels through it
+template <int MODE, class F>
+void with_act_instance(const ActArgs& a, F&& f) {
+  with_slots<8, 16, 32>(a.N, [&](auto ns) {
+    with_scenario<MODE != MODE_Q>(a.scenario, [&](auto sc) {
+      with_net<MODE != MODE_STEP>(a.net, [&](auto net) {
+        with_spec<ActSpecs<decltype(ns)::value, MODE, decltype(sc)::value, decltype(net)::value>>(
+            a.graph, a.conv, [&](auto sp) { f(ns, sc, net, sp); });
+      });
+    });
+  });
+}
 // tick_kernel<NSA = 8 or 16, td_wave_slots(NSA), NSA, SCEN, SPEC>: the complete graph, radius + GAT
 template <int NSA, int SCEN>
 struct TickSpecs {

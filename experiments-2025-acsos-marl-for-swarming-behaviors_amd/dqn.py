@@ -9,6 +9,13 @@ as ``experiment_{experiment}-seed_{seed}.pth`` (:201) and the stats CSV with the
 reference's ``i // 10`` indexing (:225-231).  One episode is captured once into a
 hipGraph and replayed.
 
+Optional evaluation inside training (not in the reference, whose training loop never evaluates):
+with ``config["eval_every"] = E`` every E-th episode ends with a greedy rollout of the current
+weights on ``eval_envs`` evaluation environments (``eval_seed``; ``eval_graph`` / ``eval_knn_k``
+default to the training graph), one row per evaluation in ``trainer.eval_rows`` and in
+``experiment_{experiment}-seed_{seed}-eval.csv``.  A ``PopulationTrainer`` evaluates all its
+members in one launch (``SwarmPopulation.evaluate``).  Training itself keeps every bit.
+
 Deliberate, documented differences (SURVEY §7 "RNG", "Vectorisation fixes"):
 random draws come from Philox keyed by (seed, tick, env), not Python ``random``;
 with ``num_envs`` > 1 each env draws its own exploration coin.
@@ -28,7 +35,7 @@ from . import _lib
 from .engine import SwarmEngine, flatten_state_dict, glorot_init, unflatten_params
 from .gcn import GCN
 from .graph import Batch, Data, create_graph_from_observations
-from .population import SwarmPopulation
+from .population import SwarmPopulation, evaluation_engine
 
 
 class SummaryWriter:
@@ -124,6 +131,8 @@ class DQNTrainer:
         self.episode_obstacle_hits = []
         self.rewards_buffer = []
         self.obstacle_hits_buffer = []
+        self.eval_rows = []     # (episode, mean reward per tick, hits, final distance) per evaluation
+        self._eval_engine = None
 
     def create_graph_from_observations(self, observations) -> Data:
         return create_graph_from_observations(observations)
@@ -178,8 +187,27 @@ class DQNTrainer:
         if self.engine.peer is not None:
             self.engine.peer.check()   # an expired peer-exchange wait: the summed gradient is wrong
 
+    def _evaluate(self, ev: dict, n_ticks: int):
+        """The lone trainer's evaluation: swarm_env_reset + swarm_rollout on an evaluation engine of
+        its own, with the training engine's weights as they stand (no flush)."""
+        if self._eval_engine is None or self._eval_key != tuple(ev.values()):
+            self._eval_engine = evaluation_engine(self.engine.cfg, ev["envs"], ev["seed"], ev["graph"], ev["knn_k"])
+            self._eval_key = tuple(ev.values())
+        e = self._eval_engine
+        e.reset(0)
+        res = e.rollout(n_ticks, tick0=0, eps=0.0, params=self.engine.params)
+        return [{k: v.cpu() for k, v in res.items()}]
+
     def train_model(self, config):
         _train_loop(self, self.engine, [self], (), config, "", "Model saved successfully!")
+
+    def save_eval_to_csv(self):
+        os.makedirs(self.stats_path, exist_ok=True)
+        with open(f"{self.stats_path}/experiment_{self.experiment}-seed_{self.seed}-eval.csv", mode="w",
+                  newline="") as f:
+            w = csv.writer(f)
+            w.writerow(["Episode", "Reward", "Collisions", "Distance (end)"])
+            w.writerows(self.eval_rows)
 
     def save_metrics_to_csv(self):
         os.makedirs(self.stats_path, exist_ok=True)
@@ -236,6 +264,13 @@ class PopulationTrainer:
     def _check_episode(self):
         self.population.check_handoffs()
 
+    def _evaluate(self, ev: dict, n_ticks: int):
+        """Every member's evaluation in one launch (DQNTrainer._evaluate's rows, member by member)"""
+        res = self.population.evaluate(ev["envs"], n_ticks, seed=ev["seed"], episode=0, graph=ev["graph"],
+                                       knn_k=ev["knn_k"])
+        res = {k: v.cpu() for k, v in res.items()}
+        return [{k: v[m] for k, v in res.items()} for m in range(self.population.P)]
+
     def train_model(self, config):
         _train_loop(self, self.population, self.trainers, (self.population.P,), config, "Seed {seed}, ",
                     "Models saved successfully!")
@@ -243,6 +278,15 @@ class PopulationTrainer:
 
 def _is_sequence(v) -> bool:
     return isinstance(v, (list, tuple)) or hasattr(v, "tolist") and getattr(v, "ndim", 0) > 0
+
+
+def eval_row(episode: int, res: dict, n_ticks: int) -> tuple:
+    """(episode, mean reward per tick, hits, final distance) of one policy's evaluation rollout
+    (host tensors of ``SwarmEngine.rollout``): Simulator's result.csv columns (the agents' summed
+    reward per tick, the hits summed over the ticks, the last tick's mean goal distance), each a
+    mean over the evaluation environments."""
+    return (episode, float(res["reward"].sum(dim=1).mean()) / max(n_ticks, 1), float(res["hits"].mean()),
+            float(res["avg_dist"].mean()))
 
 
 def _train_loop(driver, group, trainers, shape, config, prefix: str, saved: str):
@@ -263,6 +307,11 @@ def _train_loop(driver, group, trainers, shape, config, prefix: str, saved: str)
     initial_epsilon, epsilon_decay, min_epsilon = schedule
     episodes = config["episodes"]
     max_steps = first.env.max_steps or 100
+    eval_every = config.get("eval_every")   # absent or None: no evaluation
+    if eval_every is not None and (isinstance(eval_every, bool) or int(eval_every) != eval_every or eval_every < 1):
+        raise ValueError(f"eval_every must be an integer >= 1 or None, not {eval_every!r}")
+    ev = dict(envs=config.get("eval_envs", 8), seed=config.get("eval_seed", 6967), graph=config.get("eval_graph"),
+              knn_k=config.get("eval_knn_k"))
     epsilon = initial_epsilon
     driver._acc_reward = torch.zeros(shape, device=group.device)
     driver._acc_loss = torch.zeros(shape, device=group.device)
@@ -309,12 +358,17 @@ def _train_loop(driver, group, trainers, shape, config, prefix: str, saved: str)
             print(f"{prefix.format(seed=t.seed)}Episode {episode}, Loss: {average_loss}, "
                   f"Reward: {ep_reward * t.env.n_agents}, Epsilon: {epsilon[m] if per_member_eps else epsilon}")
         ticks += max_steps
+        if eval_every is not None and (episode + 1) % eval_every == 0:
+            for t, res in zip(trainers, driver._evaluate(ev, max_steps)):
+                t.eval_rows.append(eval_row(episode, res, max_steps))
     print("Training completed")
     for t in trainers:
         t._sync_models()
         os.makedirs(t.models_path, exist_ok=True)
         torch.save(t.model.state_dict(), f"{t.models_path}/experiment_{t.experiment}-seed_{t.seed}.pth")
         t.save_metrics_to_csv()
+        if eval_every is not None:
+            t.save_eval_to_csv()
     print(saved)
 
 

@@ -19,6 +19,11 @@ every member's control block, reward, avg_dist, hits and hand-off workspace into
 contiguous ``[P, ...]`` tensors, so the per-tick bookkeeping of a trainer is a fixed number of
 launches whatever P is.  Members never exchange data: member m computes bit for bit what a lone
 ``SwarmEngine`` with its seed computes with ``train_tick`` (tests/test_gpu_population.py).
+
+Evaluation has the same shape (1-8 environments per policy, one or two blocks per rollout launch):
+``ActorPopulation`` rolls out P existing engines in one swarm_pop_rollout launch, grid
+(ceil(B / 4), P), and ``SwarmPopulation.evaluate`` runs every member's current weights on one set
+of evaluation environments that way (tests/test_gpu_pop_rollout.py).
 """
 from __future__ import annotations
 
@@ -27,8 +32,10 @@ from typing import Sequence
 
 import torch
 
-from ._lib import CTRL, SwarmAdamCfg, SwarmConfig, SwarmPopMember, call, ptr
-from .engine import HP_FIELDS, SwarmEngine, capture_ticks, check_hp_values, decode_ctrl, norm_flags
+from . import _lib
+from ._lib import CTRL, SwarmActOut, SwarmAdamCfg, SwarmConfig, SwarmPopActor, SwarmPopMember, call, ptr, size
+from .engine import (CONVS, GRAPHS, HP_FIELDS, NETS, SwarmEngine, capture_ticks, check_hp_values, decode_ctrl,
+                     norm_flags)
 
 
 def _bytes_of(struct) -> bytes:
@@ -146,6 +153,7 @@ class SwarmPopulation:
         rows = (SwarmAdamCfg * P)(*[self._row(e) for e in members])
         self._hp_table = torch.frombuffer(bytearray(_bytes_of(rows)), dtype=torch.uint8).to(dev).view(P, -1)
         self.per_member_hp = self._rows_differ()
+        self._evals = {}   # evaluate(): (n_envs, graph, knn_k) -> its launches, start and state rows
 
     @staticmethod
     def _row(e) -> SwarmAdamCfg:
@@ -247,3 +255,181 @@ class SwarmPopulation:
         """Every member's control block as SwarmEngine.read_ctrl gives it; one device read."""
         c = self.ctrl.cpu()
         return [decode_ctrl(c[m]) for m in range(self.P)]
+
+    # ------------------------------------------------------------------ evaluation
+    def evaluate(self, n_envs: int, n_ticks: int, *, seed: int, episode: int = 0, graph=None, knn_k=None,
+                 eps: float = 0.0):
+        """A rollout (greedy while ``eps`` is 0) of every member's current weights on ``n_envs``
+        evaluation environments, the same for every member: one reset keyed (``seed``,
+        ``episode``) whose start is copied to every member's row of an evaluation state buffer,
+        then one swarm_pop_rollout launch.  ``graph`` / ``knn_k``: the evaluation graph (default the
+        training graph's).  Returns ``ActorPopulation.rollout``'s dict ([P, ...] device tensors,
+        the population's own buffers: the next evaluation of the same shape overwrites them).
+
+        It reads ``members[m].params`` as they stand, with no ``flush``: after a tick's two
+        launches that row holds the weights the tick acted with, and a pending optimizer step
+        stays pending.  It writes only its own state and output buffers (built once per shape), so
+        the training run keeps every bit: control blocks, replay rings, env states, Philox streams.
+        Row m equals ``evaluation_engine(members[m].cfg, ...)``'s lone reset + rollout."""
+        key = (n_envs, graph, knn_k)
+        ev = self._evals.get(key)
+        if ev is None:
+            cfg = evaluation_config(self.cfg, n_envs, graph, knn_k)
+            nst = max(size(self.lib, "swarm_state_floats", cfg), 1)
+            ev = self._evals[key] = (_PopRollout(self.lib, self.device, cfg, self.P),
+                                     torch.zeros(nst, dtype=torch.float32, device=self.device),
+                                     torch.zeros(self.P, nst, dtype=torch.float32, device=self.device))
+        roll, start, states = ev
+        roll.cfg.seed = seed & 0xFFFFFFFFFFFFFFFF
+        call(self.lib, "swarm_env_reset", roll.cfg, ptr(start), episode)
+        states.copy_(start.expand_as(states))
+        res = roll.prepare(n_ticks, [roll.cfg.seed] * self.P, [ptr(e.params) for e in self.members],
+                           [ptr(states[m]) for m in range(self.P)], 0, eps, False)
+        roll.launch(n_ticks)
+        return res
+
+
+def evaluation_config(cfg: SwarmConfig, n_envs: int, graph=None, knn_k=None) -> SwarmConfig:
+    """The configuration a learner of ``cfg`` is evaluated with: ``n_envs`` environments that each
+    draw their own start (no shared reset centre), the graph ``graph`` / ``knn_k`` (names of
+    ``engine.GRAPHS``; default ``cfg``'s own), everything else as trained."""
+    c = _copy_of(cfg)
+    c.n_envs, c.env_offset = n_envs, 0
+    c.flags &= ~_lib.F_SHARED_RESET
+    if graph is not None:
+        c.graph = GRAPHS[graph]
+    if knn_k is not None:
+        c.knn_k = knn_k
+    return c
+
+
+def evaluation_engine(cfg: SwarmConfig, n_envs: int, seed: int, graph=None, knn_k=None) -> SwarmEngine:
+    """A lone acting engine of ``evaluation_config`` (a lone trainer's evaluation; the reference
+    side of ``SwarmPopulation.evaluate``)."""
+    c = evaluation_config(cfg, n_envs, graph, knn_k)
+    names = lambda table, v: next(k for k, x in table.items() if x == v)   # noqa: E731
+    return SwarmEngine(c.scenario, c.n_agents, n_envs, seed=seed, graph=names(GRAPHS, c.graph), knn_k=c.knn_k,
+                       conv=names(CONVS, c.conv), radius=c.radius, learn=False, shared_reset=False,
+                       random_oa=bool(c.flags & _lib.F_RANDOM_OA), eps=0.0, net=names(NETS, c.net),
+                       params=torch.zeros(_lib.GAT3_N_PARAMS if c.net == _lib.NET_GAT3 else _lib.N_PARAMS))
+
+
+def _per_actor(v, P: int, name: str) -> list:
+    """one value for all actors, or a sequence of P"""
+    if hasattr(v, "tolist"):
+        v = v.tolist()
+    if not isinstance(v, (tuple, list)):
+        return [v] * P
+    if len(v) != P:
+        raise ValueError(f"{name}: {len(v)} values for {P} actors")
+    return list(v)
+
+
+class _PopRollout:
+    """swarm_pop_rollout launches of one configuration and P actors: the descriptor table in
+    device memory and the [P, ...] result buffers the descriptors point into."""
+
+    def __init__(self, lib, device, cfg: SwarmConfig, P: int):
+        self.lib, self.device, self.cfg, self.P = lib, device, _copy_of(cfg), P
+        self.table = torch.zeros(P * ctypes.sizeof(SwarmPopActor), dtype=torch.uint8, device=device)
+        self._written = None   # the table's bytes as last copied to the device
+        self._results = {}     # (n_ticks, traj) -> result dict
+
+    def results(self, n_ticks: int, traj: bool) -> dict:
+        res = self._results.get((n_ticks, traj))
+        if res is None:
+            P, B, N = self.P, self.cfg.n_envs, self.cfg.n_agents
+            shapes = dict(reward=(P, B, N), hits=(P, B), avg_dist=(P, B), obs=(P, B, N, 6))
+            if traj:
+                shapes.update(traj_pos=(P, n_ticks, B, N, 2), traj_dist=(P, n_ticks, B), traj_hits=(P, n_ticks, B))
+            res = self._results[n_ticks, traj] = {k: torch.zeros(s, device=self.device) for k, s in shapes.items()}
+        return res
+
+    def prepare(self, n_ticks: int, seeds, params, states, tick0, eps, traj: bool) -> dict:
+        """Bring the device table in line with the arguments (pointers as integers; tick0 and eps
+        one value or P) and return the result dict the next launch fills.  The table is copied to
+        the device only when its bytes changed: a launch with the arguments of the one before
+        touches nothing but the kernel's own buffers, so it can be captured and replayed; a
+        ``prepare`` with new arguments between two replays holds from the next replay on."""
+        P = self.P
+        tick0, eps = _per_actor(tick0, P, "tick0"), _per_actor(eps, P, "eps")
+        res = self.results(n_ticks, traj)
+        arr = (SwarmPopActor * P)()
+        for m in range(P):
+            out = SwarmActOut(0, 0, ptr(res["reward"][m]), ptr(res["obs"][m]), ptr(res["avg_dist"][m]),
+                              ptr(res["hits"][m]), 0, *[ptr(res[k][m]) if traj else 0
+                                                        for k in ("traj_pos", "traj_dist", "traj_hits")])
+            arr[m] = SwarmPopActor(seeds[m], params[m], states[m], out, int(tick0[m]) & 0xFFFFFFFF, float(eps[m]))
+        raw = _bytes_of(arr)
+        if raw != self._written:
+            self.table.copy_(torch.frombuffer(bytearray(raw), dtype=torch.uint8))   # on the current stream
+            self._written = raw
+        return res
+
+    def launch(self, n_ticks: int):
+        if n_ticks == 0:   # nothing is written: a lone rollout's fresh (zero) results
+            for traj in (False, True):
+                for v in self._results.get((0, traj), {}).values():
+                    v.zero_()
+        call(self.lib, "swarm_pop_rollout", self.cfg, ptr(self.table), self.P, n_ticks)
+
+
+class ActorPopulation:
+    """P policies rolled out together: ``engines`` are existing ``SwarmEngine``s (``learn=False``
+    or learners) on one device that share one configuration apart from the seed; ``rollout`` runs
+    ``SwarmEngine.rollout`` of every one of them in ONE swarm_pop_rollout launch.  Row m of every
+    result, and engine m's ``state`` / ``scenario_state`` afterwards, are bit for bit what
+    ``engines[m].rollout(...)`` gives (tests/test_gpu_pop_rollout.py)."""
+
+    def __init__(self, engines: Sequence[SwarmEngine]):
+        engines = list(engines)
+        if not engines:
+            raise ValueError("an actor population needs at least one engine")
+        first = engines[0]
+
+        def shared(e):
+            c = _copy_of(e.cfg)
+            c.seed = 0
+            return _bytes_of(c), e.device
+        for e in engines:
+            if shared(e) != shared(first):
+                raise ValueError("the engines of an actor population share one device and one configuration (all "
+                                 "but the seed): agents, envs, scenario, graph, conv, net")
+        if len({id(e) for e in engines}) != len(engines):
+            raise ValueError("an engine can be an actor only once")
+        self.engines = engines
+        self.P, self.B, self.N = len(engines), first.B, first.N
+        self.lib, self.device = first.lib, first.device
+        self._roll = _PopRollout(self.lib, self.device, first.cfg, self.P)
+        self._params = None
+
+    def prepare(self, n_ticks: int, tick0=0, eps=0.0, traj: bool = False, params=None) -> dict:
+        """``rollout`` without the launch: the descriptor table is brought in line with the
+        arguments (copied to the device only if they differ from the last call's) and the result
+        dict is returned.  Between two replays of a captured ``rollout`` it changes what the next
+        replay runs with (``n_ticks`` and ``traj`` are the capture's own)."""
+        P = self.P
+        if params is None:
+            rows = [e.params for e in self.engines]
+        else:
+            n_par = self.engines[0].params.numel()
+            if len(params) != P or (hasattr(params, "dim") and params.dim() != 2):
+                raise ValueError(f"params: a [P, {n_par}] tensor or a list of {P} tensors")
+            rows = [params[m] for m in range(P)]
+            for r in rows:
+                if r.numel() != n_par or r.dtype != torch.float32 or r.device != self.device or not r.is_contiguous():
+                    raise ValueError(f"params: {n_par} contiguous float32 values on {self.device} per actor")
+        self._params = rows   # kept alive while the table names them
+        return self._roll.prepare(n_ticks, [e.cfg.seed for e in self.engines], [ptr(r) for r in rows],
+                                  [ptr(e.state) for e in self.engines], tick0, eps, traj)
+
+    def rollout(self, n_ticks: int, tick0=0, eps=0.0, traj: bool = False, params=None) -> dict:
+        """``SwarmEngine.rollout`` of every engine in one launch: the same dict with a leading [P]
+        dimension.  ``tick0`` and ``eps``: one value or P; ``params``: None (each engine's live
+        ``params``), a [P, n_par] tensor or a list of P tensors.  The tensors returned are the
+        population's own buffers, one set per (n_ticks, traj): the next rollout of that shape
+        overwrites them.  The device descriptor table is rewritten only when an argument changed,
+        so a rollout called once eagerly can then be captured and replayed (``prepare``)."""
+        res = self.prepare(n_ticks, tick0, eps, traj, params)
+        self._roll.launch(n_ticks)
+        return res

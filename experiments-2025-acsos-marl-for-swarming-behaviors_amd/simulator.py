@@ -9,6 +9,10 @@ reference's committed outputs were produced with 5.  ``graph="radiu
 reference).
 With ``num_envs`` > 1, metrics are averaged over envs and trajectories of env 0
 are written.
+
+``PopulationSimulator`` runs the same loop for several models on one env (the evaluation grid's
+model seeds on the same starts): per episode one reset and ONE ``swarm_pop_rollout`` launch for
+all models; every model's files are what a lone ``Simulator`` writes.
 """
 from __future__ import annotations
 
@@ -20,6 +24,7 @@ import time
 import torch
 
 from . import _lib
+from .population import _PopRollout
 
 
 class Simulator:
@@ -51,33 +56,41 @@ class Simulator:
             raise RuntimeError("selected index k out of range")
         eng = self.env.engine
         params = self.model.flat_params(eng.device)
-        conv = _lib.CONV_GAT if getattr(self.model, "conv", "gat") == "gat" else _lib.CONV_GCN
         saved = (eng.cfg.graph, eng.cfg.knn_k, eng.cfg.conv, eng.cfg.radius, eng.cfg.net)
-        eng.cfg.graph, eng.cfg.knn_k, eng.cfg.conv, eng.cfg.radius = self.graph, self.knn_k, conv, self.radius
-        eng.cfg.net = getattr(self.model, "net_id", _lib.NET_GCN)   # the Flocking checkpoints' GAT3
+        eng.cfg.graph, eng.cfg.knn_k, eng.cfg.conv, eng.cfg.radius, eng.cfg.net = self._evaluation_cfg()
         T = self.env.max_steps
         try:
             for episode in range(self.episodes):
                 self.env.reset()
                 t0 = time.time()
                 res = eng.rollout(T, tick0=episode * T, eps=0.0, traj=True, params=params)
-                pos = res["traj_pos"][:, 0].cpu()            # [T, N, 2] env 0
-                dist = res["traj_dist"].mean(dim=1).cpu()     # [T]
-                hits = res["traj_hits"].mean(dim=1).cpu()
-                total_reward = res["reward"].sum(dim=1).mean()
-                self.all_positions_x.append(pos[:, :, 0].tolist())
-                self.all_positions_y.append(pos[:, :, 1].tolist())
-                self.all_distances.append(dist.tolist())
-                self.all_hits.append(hits.tolist())
-                print(f"It took: {time.time() - t0}s for {T} steps of episode {episode} with "
-                      f"{float(total_reward)} total reward, on device {eng.device} for test_gcn_vmas scenario.")
-                self.total_collisions.append(hits.sum())
-                self.distance_at_the_end.append(dist[-1])
-                self.distance_at_the_beginning.append(dist[0])
-                self.episode_rewards.append(float(total_reward) / T)
+                self._record_episode(res, episode, T, t0)
         finally:
             eng.cfg.graph, eng.cfg.knn_k, eng.cfg.conv, eng.cfg.radius, eng.cfg.net = saved
         self.save_metrics_to_csv()
+
+    def _evaluation_cfg(self):
+        """(graph, knn_k, conv, radius, net) of the engine's configuration while this model runs"""
+        conv = _lib.CONV_GAT if getattr(self.model, "conv", "gat") == "gat" else _lib.CONV_GCN
+        net = getattr(self.model, "net_id", _lib.NET_GCN)   # the Flocking checkpoints' GAT3
+        return self.graph, self.knn_k, conv, self.radius, net
+
+    def _record_episode(self, res, episode, T, t0):
+        """one episode's rollout results (``SwarmEngine.rollout`` with traj=True) into the lists"""
+        pos = res["traj_pos"][:, 0].cpu()            # [T, N, 2] env 0
+        dist = res["traj_dist"].mean(dim=1).cpu()     # [T]
+        hits = res["traj_hits"].mean(dim=1).cpu()
+        total_reward = res["reward"].sum(dim=1).mean()
+        self.all_positions_x.append(pos[:, :, 0].tolist())
+        self.all_positions_y.append(pos[:, :, 1].tolist())
+        self.all_distances.append(dist.tolist())
+        self.all_hits.append(hits.tolist())
+        print(f"It took: {time.time() - t0}s for {T} steps of episode {episode} with "
+              f"{float(total_reward)} total reward, on device {self.env.engine.device} for test_gcn_vmas scenario.")
+        self.total_collisions.append(hits.sum())
+        self.distance_at_the_end.append(dist[-1])
+        self.distance_at_the_beginning.append(dist[0])
+        self.episode_rewards.append(float(total_reward) / T)
 
     def save_metrics_to_csv(self):
         where = self.output_dir
@@ -105,3 +118,49 @@ class Simulator:
                 w.writerow(["Tick", "Distance", "Hits"])
                 for j in range(len(self.all_distances[i])):
                     w.writerow([j, self.all_distances[i][j], self.all_hits[i][j]])
+
+
+class PopulationSimulator:
+    """``Simulator.run_simulation`` for several models on one env: ``models[m]``'s outputs go to
+    ``output_dirs[m]``.  Each episode is one ``env.reset()``; the start (Flocking's stored spread
+    included) is copied into one state buffer per model, and one ``swarm_pop_rollout`` launch runs
+    every model's ``max_steps`` ticks.  Every file is byte for byte what a lone ``Simulator`` with
+    that model writes from a fresh env of the same seed (tests/test_gpu_pop_rollout.py).  The
+    models must share the conv and the net (one configuration per launch).  The env's own state
+    stays at the episode's start."""
+
+    def __init__(self, env, models, episodes, env_name, seed, output_dirs, knn_k: int = 10, graph: str = "knn",
+                 radius: float = 0.3):
+        models, output_dirs = list(models), list(output_dirs)
+        if not models or len(models) != len(output_dirs):
+            raise ValueError("one output directory per model, and at least one model")
+        self.env = env
+        self.simulators = [Simulator(env, m, episodes, env_name, seed, output_dir=d, knn_k=knn_k, graph=graph,
+                                     radius=radius) for m, d in zip(models, output_dirs)]
+        if len({s._evaluation_cfg() for s in self.simulators}) != 1:
+            raise ValueError("the models of a PopulationSimulator share one conv and one net")
+        self.episodes = episodes
+
+    def run_simulation(self):
+        first = self.simulators[0]
+        if first.graph == _lib.GRAPH_KNN and first.knn_k > self.env.n_agents:
+            raise RuntimeError("selected index k out of range")
+        eng = self.env.engine
+        P, T = len(self.simulators), self.env.max_steps
+        params = [s.model.flat_params(eng.device).contiguous() for s in self.simulators]
+        roll = _PopRollout(eng.lib, eng.device, eng.cfg, P)
+        c = roll.cfg
+        c.graph, c.knn_k, c.conv, c.radius, c.net = first._evaluation_cfg()
+        start = eng._state_buf
+        states = torch.zeros(P, start.numel(), dtype=torch.float32, device=eng.device)
+        for episode in range(self.episodes):
+            self.env.reset()
+            t0 = time.time()
+            states.copy_(start.expand_as(states))
+            res = roll.prepare(T, [eng.cfg.seed] * P, [p.data_ptr() for p in params],
+                               [states[m].data_ptr() for m in range(P)], episode * T, 0.0, True)
+            roll.launch(T)
+            for m, sim in enumerate(self.simulators):
+                sim._record_episode({k: v[m] for k, v in res.items()}, episode, T, t0)
+        for sim in self.simulators:
+            sim.save_metrics_to_csv()

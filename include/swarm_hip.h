@@ -405,6 +405,35 @@ int swarm_adam_flush(const swarm_config* cfg, const swarm_adam_cfg* hp, const sw
 int swarm_rollout(const swarm_config* cfg, const float* params, float* state,
                   int32_t n_ticks, uint32_t tick0, float eps, const swarm_act_out* out, void* stream);
 
+/* ---- Population rollouts: n_actors >= 1 policies evaluated in ONE launch (the reference's
+ * evaluation grid runs Simulator.run_simulation, simulator.py:59-93, once per model seed on the
+ * same environments; picking a population member is a greedy rollout per member).  All actors
+ * share one swarm_config except the seed (cfg->seed is not used).  Each actor owns the rest, named
+ * by one descriptor: what swarm_rollout takes for a lone policy.  The caller keeps an array of
+ * n_actors descriptors in DEVICE memory; the kernel reads it on every launch, so a descriptor
+ * rewritten between two launches (tick0, eps, another params pointer ...) holds from the next
+ * launch on, the next replay of a captured hipGraph included.  Actors never exchange data and
+ * must not share a state or output buffer. */
+typedef struct swarm_pop_actor {
+  uint64_t seed;        /* Philox key of this actor's coin / random actions (cfg->seed is not used) */
+  const float* params;  /* swarm_n_params() floats (409 for SWARM_NET_GAT3)                         */
+  float* state;         /* swarm_state_floats(cfg) floats; advanced n_ticks ticks, as swarm_rollout does */
+  swarm_act_out out;    /* any pointer may be NULL; same meaning and layout as swarm_rollout's      */
+  uint32_t tick0;       /* tick t is keyed tick0 + t                                                */
+  float eps;
+} swarm_pop_actor;
+
+/* swarm_rollout for every actor in ONE launch, grid (ceil(n_envs / 4), n_actors): block (x, m)
+ * does for actor m what block x of swarm_rollout does, with the same kernel set, so actor m
+ * computes bit for bit what swarm_rollout computes with cfg->seed = actors[m].seed and the
+ * actor's params, state, tick0, eps and out (tests/test_gpu_pop_rollout.py).
+ * Checks, in this order: a NULL cfg or actors, or n_actors outside 1..65535: SWARM_E_BADARG; then
+ * every configuration returns what swarm_rollout returns for it; n_ticks < 0: SWARM_E_BADARG;
+ * n_ticks = 0 or n_envs = 0 returns 0 and writes nothing.  The descriptors are device memory the
+ * entry point cannot look into: valid pointers are the caller's contract. */
+int swarm_pop_rollout(const swarm_config* cfg, const swarm_pop_actor* actors, int32_t n_actors,
+                      int32_t n_ticks, void* stream);
+
 /* Workspace (floats) of swarm_td_grad's per-block gradient slabs. */
 int64_t swarm_td_workspace_floats(const swarm_config* cfg, int32_t batch);
 

@@ -8,7 +8,11 @@ recorded result.csv files (tests/golden/eval_stats.json).  Start positions come 
 not torch.randn, so the comparison is of distributions (the policies themselves are pinned
 tick by tick by tests/test_gpu_parity.py::test_gpu_reproduces_recorded_reference_actions).
 
-    python tools/eval_sweep.py [out_dir] [seeds (default 0-9)] [agents (default 5-12)]
+    python tools/eval_sweep.py [out_dir] [seeds (default 0-9)] [agents (default 5-12)] [--population]
+
+``--population`` runs the model seeds of each (scenario, agent count) cell together
+(PopulationSimulator: one env, one rollout launch per episode for all seeds) instead of one
+Simulator per seed; the files and the summary are the same bytes.
 """
 import contextlib
 import io
@@ -31,27 +35,57 @@ SCEN = {"go_to": ("GoToPositionScenario", "weights_go_to", 50),
         "flocking": ("FlockingScenario", "weights_flocking", 100)}
 
 
-def run_one(scen, seed, n, out_dir, weights):
+def _env(scen, n):
+    import swarm_amd
+    cls, _, T = SCEN[scen]
+    return swarm_amd.make_env(getattr(swarm_amd, cls)(), scenario_name="test_gcn_vmas", num_envs=1,
+                              continuous_actions=False, dict_spaces=True, wrapper=None, seed=6967, n_agents=n,
+                              max_steps=T, random=True)
+
+
+def _model(scen, seed, weights):
     import swarm_amd
     from oracle import swarm_oracle as O
-    cls, wkey, T = SCEN[scen]
-    env = swarm_amd.make_env(getattr(swarm_amd, cls)(), scenario_name="test_gcn_vmas", num_envs=1,
-                             continuous_actions=False, dict_spaces=True, wrapper=None, seed=6967, n_agents=n,
-                             max_steps=T, random=True)
+    wkey = SCEN[scen][1]
     if scen == "flocking":
-        model = swarm_amd.GCN.from_state_dict(O.gat3_unflatten(torch.tensor(weights[wkey][seed])))
-    else:
-        model = swarm_amd.GCN(7, 32, 9)
-        model.load_state_dict(O.unflatten_params(torch.tensor(weights[wkey][seed])))
-    d = os.path.join(out_dir, scen, f"seed_{seed}", f"agents_{n}")
-    sim = swarm_amd.Simulator(env, model, 8, scen, 6967, output_dir=d, knn_k=5)
-    with contextlib.redirect_stdout(io.StringIO()):
-        sim.run_simulation()
+        return swarm_amd.GCN.from_state_dict(O.gat3_unflatten(torch.tensor(weights[wkey][seed])))
+    model = swarm_amd.GCN(7, 32, 9)
+    model.load_state_dict(O.unflatten_params(torch.tensor(weights[wkey][seed])))
+    return model
+
+
+def _dir(out_dir, scen, seed, n):
+    return os.path.join(out_dir, scen, f"seed_{seed}", f"agents_{n}")
+
+
+def _rows(d):
     rows = np.loadtxt(os.path.join(d, "result.csv"), delimiter=",", skiprows=1, ndmin=2)
     return rows[:, 1:5].tolist()
 
 
+def run_one(scen, seed, n, out_dir, weights):
+    import swarm_amd
+    d = _dir(out_dir, scen, seed, n)
+    sim = swarm_amd.Simulator(_env(scen, n), _model(scen, seed, weights), 8, scen, 6967, output_dir=d, knn_k=5)
+    with contextlib.redirect_stdout(io.StringIO()):
+        sim.run_simulation()
+    return _rows(d)
+
+
+def run_cell(scen, seeds, n, out_dir, weights):
+    """run_one for every seed of the cell in one PopulationSimulator; the rows in the order of seeds"""
+    import swarm_amd
+    dirs = [_dir(out_dir, scen, s, n) for s in seeds]
+    sim = swarm_amd.PopulationSimulator(_env(scen, n), [_model(scen, s, weights) for s in seeds], 8, scen, 6967, dirs,
+                                        knn_k=5)
+    with contextlib.redirect_stdout(io.StringIO()):
+        sim.run_simulation()
+    return [r for d in dirs for r in _rows(d)]
+
+
 def main():
+    population = "--population" in sys.argv
+    sys.argv = [a for a in sys.argv if a != "--population"]
     out_dir = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "gpurun_out", "eval_sweep")
     seeds = [int(s) for s in sys.argv[2].split(",")] if len(sys.argv) > 2 else list(range(10))
     agents = [int(s) for s in sys.argv[3].split(",")] if len(sys.argv) > 3 else list(range(5, 13))
@@ -66,7 +100,8 @@ def main():
         print(f"{scen}: mean over {len(seeds)} seeds x 8 episodes (ours | reference)", flush=True)
         print("  agents   reward              collisions        distance(end)     distance(begin)", flush=True)
         for n in agents:
-            ours = [r for s in seeds for r in run_one(scen, s, n, out_dir, weights)]
+            ours = (run_cell(scen, seeds, n, out_dir, weights) if population
+                    else [r for s in seeds for r in run_one(scen, s, n, out_dir, weights)])
             theirs = [r for s in range(10) for r in ref[scen][f"{s}/{n}"]] if scen in ref else None
             row = {}
             for j, name in enumerate(("reward", "collisions", "distance_end", "distance_begin")):

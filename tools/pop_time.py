@@ -13,7 +13,16 @@ size, so every timed tick trains.  The ways alternate, `--repeats` times each; t
 median and the spread in us per population tick (= one tick of all P learners).  Environment
 resets are not timed (they are per-member launches in both).
 
-usage: python tools/pop_time.py [--repeats 7] [--sizes 1,10,64] [--out population_time.json]
+``--rollout`` times evaluation instead, at the evaluation shape (kNN-5 graph, 8 envs, 100 greedy
+ticks, P policies = model seeds 0..P-1 of random weights on the same starts):
+  sequential : P lone swarm_rollout launches one after another on one stream (captured once into
+               one hipGraph, so no host time is between them): what evaluating the policies in turn costs;
+  population : one swarm_pop_rollout launch of all P (captured likewise).
+Same method: HIP events around back-to-back replays, the ways alternating, medians with min and
+max, here in us per evaluation of all P policies (one 100-tick rollout each).  The states are not
+reset between replays (both ways advance theirs alike).
+
+usage: python tools/pop_time.py [--rollout] [--repeats 7] [--sizes 1,10,64] [--out population_time.json]
 Prints one JSON line per configuration and population size.
 """
 import argparse
@@ -90,8 +99,61 @@ def measure(scen, N, P, repeats):
     return out
 
 
+def measure_rollout(scen, N, P, repeats, n_envs=8, knn_k=5):
+    kw = dict(scenario=scen, n_agents=N, n_envs=n_envs, graph="knn", knn_k=knn_k, learn=False, eps=0.0)
+    gen = torch.Generator().manual_seed(1234)
+    weights = [swarm_amd.engine.glorot_init(gen) for _ in range(P)]
+    lone = [swarm_amd.SwarmEngine(seed=6967, params=w, **kw) for w in weights]
+    acts = [swarm_amd.SwarmEngine(seed=6967, params=w, **kw) for w in weights]
+    for e in lone + acts:
+        e.reset(0)
+    pop = swarm_amd.ActorPopulation(acts)
+    pop.rollout(TICKS)   # writes the descriptor table; the captured call below finds it current
+    outs = [(e, torch.zeros(n_envs, N, device=e.device), torch.zeros(n_envs, device=e.device),
+             torch.zeros(n_envs, device=e.device)) for e in lone]
+
+    def sequential():   # what SwarmEngine.rollout launches, without its allocations
+        for e, rew, dist, hits in outs:
+            out = L.SwarmActOut(0, 0, rew.data_ptr(), 0, dist.data_ptr(), hits.data_ptr(), 0, 0, 0, 0)
+            L.call(e.lib, "swarm_rollout", e.cfg, e.params.data_ptr(), e.state.data_ptr(), TICKS, 0, 0.0, out)
+
+    dev = lone[0].device
+    graphs = {"sequential": swarm_amd.engine.capture_ticks(dev, 1, sequential),
+              "population": swarm_amd.engine.capture_ticks(dev, 1, lambda: pop.rollout(TICKS))}
+    # enough replays per window that it lasts tens of milliseconds at least
+    reps = {"sequential": max(4, math.ceil(200 / P)), "population": 200}
+
+    def window(k):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(reps[k]):
+            graphs[k].replay()
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b) * 1e3 / reps[k]
+
+    for k in graphs:
+        window(k)
+    times = {k: [] for k in graphs}
+    for _ in range(repeats):
+        for k in graphs:
+            times[k].append(window(k))
+    torch.cuda.synchronize()
+    assert all(bool(torch.isfinite(e.state).all()) for e in lone + acts)
+    out = {"mode": "rollout", "scenario": scen, "n_agents": N, "n_envs": n_envs, "graph": f"knn{knn_k}", "population": P,
+           "ticks": TICKS, "replays_per_window": reps, "repeats": repeats,
+           "build": lone[0].lib.swarm_build_info().decode()}
+    for k, v in times.items():
+        out[k + "_us"] = round(statistics.median(v), 3)
+        out[k + "_us_min_max"] = [round(min(v), 3), round(max(v), 3)]
+    out["sequential_over_population"] = round(out["sequential_us"] / out["population_us"], 3)
+    out["slowest_population_beats_fastest_sequential"] = max(times["population"]) < min(times["sequential"])
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--rollout", action="store_true", help="time evaluation rollouts instead of training ticks")
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--sizes", default="1,10,64")
     ap.add_argument("--configs", default=None, help="e.g. GoTo:5,ObstacleAvoidance:10 (default: all four)")
@@ -101,7 +163,7 @@ def main():
     rows = []
     for scen, N in configs:
         for P in [int(x) for x in a.sizes.split(",")]:
-            rows.append(measure(scen, N, P, a.repeats))
+            rows.append((measure_rollout if a.rollout else measure)(scen, N, P, a.repeats))
             print(json.dumps(rows[-1]), flush=True)
             if a.out:
                 os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

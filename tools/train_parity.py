@@ -17,6 +17,7 @@ the N the recorded runs used.  ``--agents`` sweeps it.
     python tools/train_parity.py [--out out.json] [--seeds 0,1,...] [--episodes 1000]
                                  [--scenarios GoTo,ObstacleAvoidance] [--agents 10[,5,...]]
                                  [--population [--lr 1e-3,3e-4,... --gamma 0.99,0.95,...]]
+                                 [--eval-every N]
 
 ``--population`` trains the seeds of a scenario and agent count together (PopulationTrainer: one
 launch ticks every seed) instead of one after another; the curves are the same bits.
@@ -24,6 +25,9 @@ launch ticks every seed) instead of one after another; the curves are the same b
 one value for all, or one per seed in the order of ``--seeds``.  That is a sweep in one run; each
 member's setting is recorded with its curve (``member_hp``), and the comparison with the
 reference's recorded curves then describes the sweep, not the reference's configuration.
+``--eval-every N`` ends every N-th episode with a greedy evaluation rollout of each seed's current
+weights (``eval_every`` of ``train_model``'s config; with ``--population`` one launch for all seeds);
+the rows (episode, mean reward per tick, hits, final distance) are recorded per seed (``eval_rows``).
 """
 import argparse
 import contextlib
@@ -40,7 +44,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def run(scen_name, seed, episodes, n_agents=10):
+EVAL_ROWS = {}   # (scenario, agents) -> {seed: eval_rows} of the runs with --eval-every
+
+
+def _config(episodes, eval_every):
+    cfg = {"epsilon": 0.99, "epsilon_decay": 0.01, "min_epsilon": 0.05, "episodes": episodes}
+    return cfg | ({"eval_every": eval_every} if eval_every else {})
+
+
+def run(scen_name, seed, episodes, n_agents=10, eval_every=None):
     import swarm_amd
     scen = swarm_amd.GoToPositionScenario() if scen_name == "GoTo" else swarm_amd.ObstacleAvoidanceScenario()
     env = swarm_amd.make_env(scenario=scen, num_envs=1, continuous_actions=False, wrapper=None, max_steps=100,
@@ -49,11 +61,12 @@ def run(scen_name, seed, episodes, n_agents=10):
         swarm_amd.set_seed(seed)
         tr = swarm_amd.DQNTrainer(env, seed, os.path.join(d, "models"), os.path.join(d, "stats"), scen_name)
         with contextlib.redirect_stdout(io.StringIO()):
-            tr.train_model({"epsilon": 0.99, "epsilon_decay": 0.01, "min_epsilon": 0.05, "episodes": episodes})
+            tr.train_model(_config(episodes, eval_every))
+    EVAL_ROWS.setdefault((scen_name, n_agents), {})[seed] = tr.eval_rows
     return [float(x) for x in tr.episode_rewards]
 
 
-def run_population(scen_name, seeds, episodes, n_agents=10, lr=None, gamma=None):
+def run_population(scen_name, seeds, episodes, n_agents=10, lr=None, gamma=None, eval_every=None):
     """run() for all seeds at once: {seed: curve}; lr / gamma: one value per seed, or None"""
     import swarm_amd
     with tempfile.TemporaryDirectory() as d:
@@ -67,8 +80,8 @@ def run_population(scen_name, seeds, episodes, n_agents=10, lr=None, gamma=None)
             trainers.append(swarm_amd.DQNTrainer(env, seed, os.path.join(d, "models"), os.path.join(d, "stats"),
                                                  scen_name, **hp))
         with contextlib.redirect_stdout(io.StringIO()):
-            swarm_amd.PopulationTrainer(trainers).train_model(
-                {"epsilon": 0.99, "epsilon_decay": 0.01, "min_epsilon": 0.05, "episodes": episodes})
+            swarm_amd.PopulationTrainer(trainers).train_model(_config(episodes, eval_every))
+    EVAL_ROWS[scen_name, n_agents] = {t.seed: t.eval_rows for t in trainers}
     return {t.seed: [float(x) for x in t.episode_rewards] for t in trainers}
 
 
@@ -125,6 +138,7 @@ def main():
     ap.add_argument("--population", action="store_true", help="train the seeds together (PopulationTrainer)")
     ap.add_argument("--lr", default=None, help="with --population: learning rate, one value or one per seed")
     ap.add_argument("--gamma", default=None, help="with --population: discount, one value or one per seed")
+    ap.add_argument("--eval-every", type=int, default=None, help="evaluate every N episodes (greedy rollout)")
     a = ap.parse_args()
     seeds = [int(s) for s in a.seeds.split(",")]
     sweep = {}
@@ -141,12 +155,14 @@ def main():
     for scen in a.scenarios.split(","):
         for n in [int(x) for x in a.agents.split(",")]:
             t0 = time.time()
-            ours = (run_population(scen, seeds, a.episodes, n, **sweep) if a.population
-                    else {s: run(scen, s, a.episodes, n) for s in seeds})
+            ours = (run_population(scen, seeds, a.episodes, n, eval_every=a.eval_every, **sweep) if a.population
+                    else {s: run(scen, s, a.episodes, n, a.eval_every) for s in seeds})
             secs = time.time() - t0
             r = compare(ref, scen, ours, seeds, a.episodes)
             r |= {"scenario": scen, "n_agents": n, "seconds": secs, "population": bool(a.population), "ticks": len(seeds) * a.episodes * 100,
                   "curves": {str(s): ours[s] for s in seeds}}
+            if a.eval_every:
+                r["eval_rows"] = {str(s): EVAL_ROWS[scen, n][s] for s in seeds}
             if sweep:
                 r["member_hp"] = {str(s): {k: v[i] for k, v in sweep.items()} for i, s in enumerate(seeds)}
             res["runs"].append(r)
