@@ -126,6 +126,9 @@ __device__ __forceinline__ void act_body(ActSmem<NS>& S, const int vb, const int
   }
   AdamRegs R;
   if (kLearnCT) R.load(grad, w_cur, m_cur, v_cur, threadIdx.x, true);
+  // the thread's slots of the LDS weight image, formed in the operands' flight time
+  WImageSlots wslots;
+  if (MODE == MODE_TICK && NET == SWARM_NET_GCN) wslots.form(threadIdx.x);
   // Flocking: the scenario's per-agent previous_distance_to_agents (flocking_scenario.py:110-122,
   // 163-164), kept after the [B][N][4] state as [B][N] floats (swarm_hip.h, swarm_env_reset)
   float* fl_prev = (SCEN == SWARM_FLOCKING && MODE != MODE_Q) ? state + (size_t)B * N * 4 : nullptr;
@@ -338,7 +341,7 @@ __device__ __forceinline__ void act_body(ActSmem<NS>& S, const int vb, const int
     if (pending)
       gn = adam_apply<21>(R, A.hp, step_size, inv_bc2, cc.one_m_beta1, cc.one_m_beta2, tid, red,
                           (A.hp.flags & SWARM_ADAM_F_NORM_PARTIALS) != 0);
-    store_w_lds(Pw, R, tid);
+    store_w_lds(Pw, R, tid, wslots);
     SWARM_STAMP(24);
     if (vb == 0) {
       store4(A.lr.w_nxt, R.w, R.wt, tid);

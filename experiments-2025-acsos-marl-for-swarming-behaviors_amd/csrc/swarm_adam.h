@@ -222,13 +222,29 @@ __device__ inline void store4(float* __restrict__ dst, const float4* src, float 
   if (tid == 0) dst[N_PARAMS - 1] = tail;
 }
 
-// padded LDS weight image (lds_index, N_LDS_PARAMS floats)
-__device__ inline void store_w_lds(float* __restrict__ lds, const AdamRegs& R, int tid) {
+// The thread's two float4 slots of the padded LDS weight image (lds_index, N_LDS_PARAMS floats),
+// as byte offsets.  They depend on the thread index alone, so a learning prologue forms them
+// right after it has issued its operand loads and pins them there: left to the compiler, the
+// address math sinks to the stores, behind the optimizer step, onto the chain every wave of the
+// block waits for at the weight barrier.  Slots past the last float4 are never stored.
+struct WImageSlots {
+  int b[kAdamNJ];
+  __device__ inline void form(int tid) {
 #pragma unroll
-  for (int j = 0; j < kAdamNJ; ++j) {
-    const int i = tid + kAdamNT * j;
-    if (i < kAdamNF4) *reinterpret_cast<float4*>(lds + lds_index(4 * i)) = R.w[j];
+    for (int j = 0; j < kAdamNJ; ++j) b[j] = 4 * lds_index_flat(4 * (tid + kAdamNT * j));
+    static_assert(kAdamNJ == 2, "two pinned slots");
+    asm volatile("" : "+v"(b[0]), "+v"(b[1]));
   }
+  __device__ inline float4* at(float* lds, int j) const {
+    return reinterpret_cast<float4*>(reinterpret_cast<char*>(lds) + b[j]);
+  }
+};
+
+// padded LDS weight image: the float4s into the thread's slots, the tail element by thread 0
+__device__ inline void store_w_lds(float* __restrict__ lds, const AdamRegs& R, int tid, const WImageSlots& ws) {
+#pragma unroll
+  for (int j = 0; j < kAdamNJ; ++j)
+    if (tid + kAdamNT * j < kAdamNF4) *ws.at(lds, j) = R.w[j];
   if (tid == 0) lds[lds_index(N_PARAMS - 1)] = R.wt;
 }
 

@@ -68,6 +68,22 @@ __host__ __device__ constexpr int lds_index(int p) {
        : L_B2 + (p - OFF_B2);
 }
 static_assert(lds_index(N_PARAMS - 1) == L_B2 + kActions - 1 && L_B2 + kActions <= N_LDS_PARAMS, "LDS image");
+// The same map without a branch: the image is the flat order plus 4 pad floats for every lin1 row
+// and every lin2 row that ends at or before p, so two clamped row counts and two adds form it
+// (lds_index's nested ranges compile into nested exec-mask regions when lanes of one wave fall
+// on different sides).  The learning prologues form their slots with it while their operands
+// are in flight (swarm_adam.h WImageSlots)
+__host__ __device__ constexpr int lds_index_flat(int p) {
+  const int r1 = (p - OFF_W1) >> 5, r2 = (p - OFF_W2) >> 5;   // arithmetic shifts: negative ahead of the rows
+  const int c1 = r1 < 0 ? 0 : (r1 > kHidden ? kHidden : r1), c2 = r2 < 0 ? 0 : (r2 > kActions ? kActions : r2);
+  return p + (kWRow - kHidden) * (c1 + c2);
+}
+constexpr bool lds_index_flat_matches() {
+  for (int p = 0; p < N_PARAMS; ++p)
+    if (lds_index_flat(p) != lds_index(p)) return false;
+  return true;
+}
+static_assert(lds_index_flat_matches(), "lds_index_flat == lds_index for every parameter");
 
 // RNG stream ids (third Philox counter word); must match oracle/philox.py
 constexpr uint32_t STREAM_COIN = 1;

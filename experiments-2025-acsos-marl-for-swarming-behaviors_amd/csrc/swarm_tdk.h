@@ -165,12 +165,14 @@ __device__ __forceinline__ void td_body(TdSmem<NS>& L, const int vb, const int32
   //      ctrl reads overlap it.  Indices are clamped into the ring: a skipped tick reads
   //      valid (unused) rows.  Fused tick: the pending Adam step's operands and ctrl first.
   AdamRegs R;
+  WImageSlots wslots;
   swarm_ctrl cc = {};
   if (FUSED) {   // the fused kernel's preloaded argument SGPRs (== X.lr / A.ctrl): no kernarg round trip first
     cc = *ctrl_pre;   // issued before any kernarg-segment load, so no wait on one delays it
     __builtin_amdgcn_sched_barrier(0);
     R.load(g_pre, w_pre, m_pre, v_pre, threadIdx.x, true);
     __builtin_amdgcn_sched_barrier(0);   // every Adam operand load issued before the first scalar wait
+    wslots.form(threadIdx.x);             // the thread's LDS image slots (both images), in the loads' flight time
   }
   // fused: the scalars the sampling, the hand-off test and the optimizer step read (ctrl's
   // write_slot, the batch size S, the Adam hyper-parameters) made opaque here, so they are
@@ -182,6 +184,14 @@ __device__ __forceinline__ void td_body(TdSmem<NS>& L, const int vb, const int32
   if (FUSED) {
     asm volatile("" : "+s"(cc.write_slot), "+s"(cc.trained), "+s"(S), "+s"(hp.beta1), "+s"(hp.beta2), "+s"(hp.eps),
                  "+s"(hp.max_norm), "+s"(hp.update_target_every), "+s"(hp.world_size), "+s"(sample_out), "+s"(ho_rec));
+  }
+  // fused: the pending step's two conditions (a held rank applies no step; a target-sync tick:
+  // a runtime division) from the same scalars, formed and pinned at that wait as well
+  uint32_t pending = 0u, sync_target = 0u;
+  if (FUSED) {
+    pending = (cc.trained != 0u && cc.peer_hold == 0u) ? 1u : 0u;
+    sync_target = (pending && (cc.tick % (uint32_t)hp.update_target_every) == 0u) ? 1u : 0u;
+    asm volatile("" : "+v"(sync_target));   // (the division's result lives in a VGPR)
   }
   const uint32_t cap = (uint32_t)capacity;
   const uint32_t ring_graphs = cap * (uint32_t)B;
@@ -267,15 +277,14 @@ __device__ __forceinline__ void td_body(TdSmem<NS>& L, const int vb, const int32
   bool live_drop[CT];   // this wave's graph was dropped after a hand-off overrun
 #pragma unroll
   for (int ct = 0; ct < CT; ++ct) live_drop[ct] = false;
-  if (FUSED) {   // the pending optimizer step (train_gcn_dqn.py:125-133), as every acting block does;
+  if constexpr (FUSED) {   // the pending optimizer step (train_gcn_dqn.py:125-133), as every acting block does;
                  // done before any hand-off wait so that none of it follows the wait
-    const bool pending = cc.trained != 0u && cc.peer_hold == 0u;   // a held rank applies no step
     if (pending)
       adam_apply(R, hp, cc.adam_step_size, cc.adam_inv_bc2, cc.one_m_beta1, cc.one_m_beta2, threadIdx.x, L.red,
                  (hp.flags & SWARM_ADAM_F_NORM_PARTIALS) != 0);
-    store_w_lds(Pon, R, threadIdx.x);
-    if (pending && (cc.tick % (uint32_t)hp.update_target_every) == 0u) store_w_lds(Ptg, R, threadIdx.x);
-    else ptg.store(Ptg, threadIdx.x);
+    store_w_lds(Pon, R, threadIdx.x, wslots);
+    if (__builtin_amdgcn_readfirstlane(sync_target)) store_w_lds(Ptg, R, threadIdx.x, wslots);
+    else ptg.store(Ptg, threadIdx.x, wslots.b);
   } else {
     pon.store(Pon, threadIdx.x);
     ptg.store(Ptg, threadIdx.x);

@@ -57,6 +57,14 @@ struct ParamStage {
     }
     if (tid == 0) lds[lds_index(N_PARAMS - 1)] = tail;
   }
+  // the same with the thread's float4 slots formed by the caller (byte offsets of
+  // lds_index(4 * (tid + j * NT)): swarm_adam.h WImageSlots)
+  __device__ inline void store(float* __restrict__ lds, int tid, const int (&slot)[NJ]) const {
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+      if (tid + j * NT < NF4) *reinterpret_cast<v4*>(reinterpret_cast<char*>(lds) + slot[j]) = v[j];
+    if (tid == 0) lds[lds_index(N_PARAMS - 1)] = tail;
+  }
 };
 static_assert(ParamStage<64>::NF4 * 4 + 1 == N_PARAMS && N_PARAMS_PAD == ParamStage<64>::NF4 * 4 + 4, "tail");
 
