@@ -381,8 +381,8 @@ __device__ __forceinline__ void act_body(ActSmem<NS>& S, const int vb, const int
     if (MODE != MODE_STEP && NET == SWARM_NET_GAT3) {
       gat3_forward<NS>(P, d, N, graph, A.k, A.radius, A.dense, V, F);
     } else if (MODE != MODE_STEP) {
-      if constexpr (kDefer) dl_forward<NS, 8, NS>(P, d, N, graph, A.k, A.radius, conv, A.dense, V, false, F, deferred0);
-      else dl_forward<NS, 8>(P, d, N, graph, A.k, A.radius, conv, A.dense, V, false, F);
+      if constexpr (kDefer) dl_forward<NS, 8, NS, spec_complete_graph(SPEC)>(P, d, N, graph, A.k, A.radius, conv, A.dense, V, false, F, deferred0);
+      else dl_forward<NS, 8, NS, spec_complete_graph(SPEC)>(P, d, N, graph, A.k, A.radius, conv, A.dense, V, false, F);
     }
     if constexpr (kDefer) {   // the deferred work's branches: pairs in contact, an exploring env
       if constexpr (kDeferForces) pair_contacts0();

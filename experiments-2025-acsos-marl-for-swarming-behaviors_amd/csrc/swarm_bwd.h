@@ -120,11 +120,7 @@ __device__ __forceinline__ void bwd_attention(const float (*H)[kRow], const DFwd
         for (int r = 0; r < 4; ++r) acc = mfma16(ah[ut][t][r], dO[ct][t][r], acc);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        // coefficient of edge u -> v, u = 16 ut + 4 p + r (registers hold every u of target v)
-        float cc[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) cc[q] = F.cf[ct][16 * ut + 4 * q + r];
-        cu[ut][r] = pick4(cc, 0, p);
+        cu[ut][r] = F.cr[ct][ut][r];   // coefficient of edge u -> v, u = 16 ut + 4 p + r (the forward's row pick)
         gv[ut][r] = acc[r];
         part = part + cu[ut][r] * gv[ut][r];
       }
@@ -135,12 +131,12 @@ __device__ __forceinline__ void bwd_attention(const float (*H)[kRow], const DFwd
     for (int ut = 0; ut < CT; ++ut)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        float dpu = 0.0f;
-        if (cu[ut][r] != 0.0f && live[ct]) {   // in-edges only (cross-graph / absent: c = 0)
-          const float de = cu[ut][r] * (gv[ut][r] - Gs);
-          const float pre = ssrc[16 * ut + 4 * p + r] + F.sdst[ct];
-          dpu = pre > 0.0f ? de : de * kLeakySlope;
-        }
+        // in-edges only (cross-graph / absent: c = 0), as selects: ssrc (a slot of this wave) is
+        // read unconditionally and the value of an edge that is none is discarded
+        const float de = cu[ut][r] * (gv[ut][r] - Gs);
+        const float pre = ssrc[16 * ut + 4 * p + r] + F.sdst[ct];
+        const float dpe = pre > 0.0f ? de : de * kLeakySlope;
+        const float dpu = (cu[ut][r] != 0.0f && live[ct]) ? dpe : 0.0f;
         dsum = dsum + dpu;
         dp[ct][ut][r] = dpu;
       }

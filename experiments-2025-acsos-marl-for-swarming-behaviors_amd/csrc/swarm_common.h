@@ -336,6 +336,8 @@ __device__ inline int spec_graph(int runtime) {
          : SPEC == SPEC_RADIUS_GAT  ? (int)SWARM_GRAPH_RADIUS
                                     : (int)SWARM_GRAPH_COMPLETE;
 }
+// the graph is the complete graph at compile time (dl_forward's UNIT)
+constexpr bool spec_complete_graph(int spec) { return spec == SPEC_COMPLETE_GAT || spec == SPEC_COMPLETE_GCN; }
 template <int SPEC>
 __device__ inline int spec_conv(int runtime) {
   return SPEC == SPEC_RUNTIME ? runtime : (SPEC == SPEC_COMPLETE_GCN ? (int)SWARM_CONV_GCN : (int)SWARM_CONV_GAT);

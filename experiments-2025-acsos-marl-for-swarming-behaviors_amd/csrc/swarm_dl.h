@@ -15,6 +15,8 @@
 // GCN.forward: src/training/train_gcn_dqn.py:59-70 (GATConv -> tanh -> lin1 -> relu
 // -> lin2); GATConv math: PyG 2.5.3 (heads 1, add_self_loops False).
 #pragma once
+#include <type_traits>
+
 #include "swarm_wpg.h"
 
 namespace swarm {
@@ -29,12 +31,71 @@ __device__ inline float row4_sum(float x) {
   return __int_as_float((int)b[0]) + __int_as_float((int)b[1]);
 }
 
-// pick v[4 k + p] for this lane's row group p (register arrays cannot be indexed by lane)
-template <int M>
-__device__ inline float pick4(const float (&v)[M], int k, int p) {
-  const float a = v[4 * k], b = v[4 * k + 1], c = v[4 * k + 2], d = v[4 * k + 3];
-  return p == 0 ? a : (p == 1 ? b : (p == 2 ? c : d));
+// x[p] for this lane's row group p (register arrays cannot be indexed by lane), b0 = p & 1,
+// b1 = p & 2: three selects of values that exist already.  Select first, compute after: a pick
+// among four products had the products sunk into its arms and became nested exec-mask regions
+template <class T>
+__device__ __forceinline__ T sel4(bool b0, bool b1, T x0, T x1, T x2, T x3) {
+  const T lo = b0 ? x1 : x0, hi = b0 ? x3 : x2;
+  return b1 ? hi : lo;
 }
+
+// Which in-edge coefficients a lane uses.  Target n = 16 ct + c has one coefficient per source
+// slot u of the wave: coef(u -> n) = cl[u % GS] where u is a slot of n's graph (u / GS == n / GS),
+// else 0 (cl[j]: the coefficient of local source j of n's graph).  Lane (c, p) reads only
+//   column pick ks      u = 4 ks + p          the aggregate's B operand and the cm image's row
+//   row pick (ut, r)    u = 16 ut + 4 p + r   bwd_attention's edge (NS % 16 == 0)
+// so it forms only those: per pick the candidates q = 0..3, one of which (q == p) it selects, and
+// one same-graph test.  GS % 4 == 0: the four candidates of a column pick are consecutive local
+// sources of ONE graph, col_g(ks), compared with the lane's n / GS; those of a row pick lie 4
+// apart, in graph row_g(ut, q), and the lane compares row_g(ut, p).  proved(): for every lane and
+// every pick, the same (graph, local source) as the full table's entry, and 0 exactly where that is 0.
+template <int NS, int GS>
+struct CoefPick {
+  static constexpr int CT = (NS + 15) / 16;
+  static_assert(GS % 4 == 0 && NS % GS == 0, "a pick's four candidates lie in one graph, 1 or 4 apart");
+  static constexpr int col_j(int ks, int q) { return (4 * ks) % GS + q; }
+  static constexpr int col_g(int ks) { return (4 * ks) / GS; }
+  static constexpr int row_j(int ut, int q, int r) { return (16 * ut + 4 * q) % GS + r; }
+  static constexpr int row_g(int ut, int q) { return (16 * ut + 4 * q) / GS; }
+  static constexpr bool same(int u, int n) { return u / GS == n / GS; }   // the full table's test
+  static constexpr bool proved() {
+    for (int ct = 0; ct < CT; ++ct)
+      for (int c = 0; c < 16; ++c)
+        for (int p = 0; p < 4; ++p) {
+          const int n = 16 * ct + c;
+          for (int ks = 0; ks < NS / 4; ++ks) {
+            const int u = 4 * ks + p, j = col_j(ks, p);
+            if (j < 0 || j >= GS) return false;
+            if ((col_g(ks) == n / GS) != same(u, n)) return false;
+            if (same(u, n) && j != u % GS) return false;
+          }
+          if (NS % 16 != 0) continue;
+          for (int ut = 0; ut < CT; ++ut)
+            for (int r = 0; r < 4; ++r) {
+              const int u = 16 * ut + 4 * p + r, j = row_j(ut, p, r);
+              if (u >= NS || j < 0 || j >= GS) return false;
+              if ((row_g(ut, p) == n / GS) != same(u, n)) return false;
+              if (same(u, n) && j != u % GS) return false;
+            }
+        }
+    return true;
+  }
+};
+
+// the complete graph's multiplicity of local edge j -> jn (train_gcn_dqn.py:101-108): every
+// ordered pair once, and the (0, 0) self loop in place of the missing j == jn term.  It is 0 or
+// 1, so the softmax carries it as a predicate: den + 1.0f * e and 1.0f * (e * inv) are den + e and
+// e * inv bit for bit, and an absent edge's e is masked to +0 before either
+constexpr int complete_mult(int j, int jn) { return (int)(j != jn) + (int)(j == 0 && jn == 0); }
+constexpr bool complete_edge(int j, int jn) { return j == 0 || j != jn; }
+constexpr bool complete_mult_is_edge(int gs) {
+  for (int j = 0; j < gs; ++j)
+    for (int jn = 0; jn < gs; ++jn)
+      if (complete_mult(j, jn) != (complete_edge(j, jn) ? 1 : 0)) return false;
+  return true;
+}
+static_assert(complete_mult_is_edge(32), "complete graph: multiplicity == in-edge predicate, 0 or 1");
 
 template <int NS>
 struct DGeom {
@@ -62,7 +123,11 @@ struct DFwd {
   float x[CT][2];            // X[n][p], X[n][4 + p] (features: px py vx vy gx gy id 0)
   float t[CT][2][4];         // tanh(conv out)
   float zr[CT][2][4];        // relu(lin1)
-  float cf[CT][NS];          // attention coefficient of the in-edge u -> n (0 if none)
+  // coefficients of the in-edges u -> n (0 if none), the lane's own picks (CoefPick):
+  float cc[CT][NS / 4];      // u = 4 ks + p
+  // u = 16 ut + 4 p + r.  Written for GAT with NS % 16 == 0 only (dead without a backward);
+  // bwd_attention, its one reader, has both as preconditions: GCNConv and 8-slot waves leave it unset
+  float cr[CT][CT][4];
   float sdst[CT];            // destination score of n
   float q[CT][kActions];     // Q row of n
 };
@@ -102,7 +167,7 @@ __device__ inline void in_mults(int n, int N, int graph, const WSmall<NS>& sm, c
   const bool tv = jn < N;
   if (graph == SWARM_GRAPH_COMPLETE) {
 #pragma unroll
-    for (int j = 0; j < GS; ++j) m[j] = (tv && j < N) ? (int)(j != jn) + (int)(j == 0 && jn == 0) : 0;
+    for (int j = 0; j < GS; ++j) m[j] = (tv && j < N) ? complete_mult(j, jn) : 0;
   } else if (graph == SWARM_GRAPH_KNN) {
     const uint32_t kn = sm.knn[min(n, NS - 1)];
 #pragma unroll
@@ -396,7 +461,7 @@ __device__ inline void knn_masks_wave(int lane, int N, int k, WSmall<NS>& sm, fl
 
 // Full GCN.forward.  F.x must hold the lane's features (zero for nodes >= N).  P is the
 // padded LDS weight image.  Writes the H rows (and T / R rows if keep_tr) of V, the
-// per-node scalars of V.sm, and leaves F.t / F.zr / F.cf / F.q for the backward.
+// per-node scalars of V.sm, and leaves F.t / F.zr / F.cc / F.cr / F.q for the backward.
 // HOOK: work of the caller that needs no result of the forward, called once between lin1's
 // operand reads and its first MFMA: straight-line code there is issued in the VALU / SALU slots
 // under the lin1 and lin2 MFMA chains (24 MFMAs that wait on each other and leave those slots
@@ -404,7 +469,10 @@ __device__ inline void knn_masks_wave(int lane, int N, int k, WSmall<NS>& sm, fl
 struct DlNoHook {
   __device__ __forceinline__ void operator()() const {}
 };
-template <int NS, int SB = -1, int GS = NS, class HOOK = DlNoHook>
+// UNIT: the graph is the complete graph at compile time (SPEC_COMPLETE_*): its 0 / 1 multiplicity
+// is carried as a predicate.  A kernel with a runtime graph keeps the m form for every graph
+// (the same bits on the complete graph, complete_mult), so each kernel holds one form only.
+template <int NS, int SB = -1, int GS = NS, bool UNIT = false, class HOOK = DlNoHook>
 __device__ inline void dl_forward(const float* __restrict__ P, const DGeom<NS>& d, int N, int graph, int k, float radius, int conv,
                                   const uint8_t* __restrict__ dense, const WView<NS>& V, bool keep_tr, DFwd<NS>& F,
                                   const HOOK& hook = HOOK()) {
@@ -492,65 +560,109 @@ __device__ inline void dl_forward(const float* __restrict__ P, const DGeom<NS>& 
   }
   // ---- in-edge coefficients of target n (every row group computes them; PyG softmax
   //      exp(e - max) / (sum + 1e-16) with duplicate edges counted by multiplicity)
+  using CP = CoefPick<NS, GS>;
+  static_assert(CP::proved(), "the lane's coefficient picks name the full table's entries");
+  const bool pb0 = (p & 1) != 0, pb1 = (p & 2) != 0;
   if (conv == SWARM_CONV_GAT) {
+    // UNIT: multiplicities 0 / 1 carried as the in-edge predicate (complete_mult); else m (0..3)
+    {
 #pragma unroll
-    for (int ct = 0; ct < CT; ++ct) {
-      const int n = 16 * ct + c, base = (GS < NS) ? (n / GS) * GS : 0;
-      float e[GS];
-      int m[GS];
-      in_mults<NS, GS>(n, N, graph, sm, dense, d.gid, m);
-      // the max over present edges as a tree (max is exact: the serial order's value, three
-      // dependent steps instead of GS)
-      float mx[GS];
+      for (int ct = 0; ct < CT; ++ct) {
+        const int n = 16 * ct + c, base = (GS < NS) ? (n / GS) * GS : 0;
+        const int ng = (GS < NS) ? n / GS : 0;
+        float e[GS];
+        int m[GS];
+        bool in[GS];
+        if constexpr (UNIT) {
+          const int jn = (GS < NS) ? n % GS : n;
 #pragma unroll
-      for (int j = 0; j < GS; ++j) {
-        e[j] = leaky(sm.ssrc[base + j] + F.sdst[ct]);
-        mx[j] = m[j] > 0 ? e[j] : -INFINITY;
+          for (int j = 0; j < GS; ++j) { in[j] = jn < N && j < N && complete_edge(j, jn); m[j] = 0; }
+        } else {
+          in_mults<NS, GS>(n, N, graph, sm, dense, d.gid, m);
+#pragma unroll
+          for (int j = 0; j < GS; ++j) in[j] = m[j] > 0;
+        }
+        // the max over present edges as a tree (max is exact: the serial order's value, three
+        // dependent steps instead of GS)
+        float mx[GS];
+#pragma unroll
+        for (int j = 0; j < GS; ++j) {
+          e[j] = leaky(sm.ssrc[base + j] + F.sdst[ct]);
+          mx[j] = in[j] ? e[j] : -INFINITY;
+        }
+#pragma unroll
+        for (int w = GS / 2; w >= 1; w >>= 1)
+#pragma unroll
+          for (int j = 0; j < w; ++j) mx[j] = fmaxf(mx[j], mx[j + w]);
+        const float emax = mx[0];
+        float den = 0.0f;
+#pragma unroll
+        for (int j = 0; j < GS; ++j) {
+          e[j] = in[j] ? __expf(e[j] - emax) : 0.0f;
+          den = UNIT ? den + e[j] : den + (float)m[j] * e[j];
+        }
+        den = den + 1e-16f;
+        const float inv = 1.0f / den;
+        // the lane's picks of m[j] * (e[j] * inv): e (and m) selected, then the products
+        auto coef = [&](float ep, int mp, bool same) -> float {
+          const float v = UNIT ? ep * inv : (float)mp * (ep * inv);
+          return same ? v : 0.0f;
+        };
+#pragma unroll
+        for (int ks = 0; ks < NS / 4; ++ks) {
+          const int j0 = CP::col_j(ks, 0), j1 = CP::col_j(ks, 1), j2 = CP::col_j(ks, 2), j3 = CP::col_j(ks, 3);
+          float v = coef(sel4(pb0, pb1, e[j0], e[j1], e[j2], e[j3]), sel4(pb0, pb1, m[j0], m[j1], m[j2], m[j3]),
+                         GS == NS || CP::col_g(ks) == ng);
+          // formed once, here: unpinned, the product and the mask are formed again behind B1 for
+          // the cm image, on the chain the tick's length follows
+          asm volatile("" : "+v"(v));
+          F.cc[ct][ks] = v;
+        }
+        if constexpr (NS % 16 == 0) {
+#pragma unroll
+          for (int ut = 0; ut < CT; ++ut)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int j0 = CP::row_j(ut, 0, r), j1 = CP::row_j(ut, 1, r), j2 = CP::row_j(ut, 2, r), j3 = CP::row_j(ut, 3, r);
+              F.cr[ct][ut][r] = coef(sel4(pb0, pb1, e[j0], e[j1], e[j2], e[j3]), sel4(pb0, pb1, m[j0], m[j1], m[j2], m[j3]),
+                                     GS == NS || CP::row_g(ut, p) == ng);
+            }
+        }
       }
-#pragma unroll
-      for (int w = GS / 2; w >= 1; w >>= 1)
-#pragma unroll
-        for (int j = 0; j < w; ++j) mx[j] = fmaxf(mx[j], mx[j + w]);
-      const float emax = mx[0];
-      float den = 0.0f;
-#pragma unroll
-      for (int j = 0; j < GS; ++j) {
-        e[j] = m[j] > 0 ? __expf(e[j] - emax) : 0.0f;
-        den = den + (float)m[j] * e[j];
-      }
-      den = den + 1e-16f;
-      const float inv = 1.0f / den;
-      float cl[GS];
-#pragma unroll
-      for (int j = 0; j < GS; ++j) cl[j] = (float)m[j] * (e[j] * inv);
-#pragma unroll
-      for (int u = 0; u < NS; ++u) F.cf[ct][u] = (GS == NS || u / GS == n / GS) ? cl[u % GS] : 0.0f;
     }
   } else {
     // GCNConv (a13, parity unpinned): self loops collapse to weight 1, symmetric deg^-1/2
     float dis[CT];
+    float wl[CT][GS];   // weight of local source j's edge into n (1 for n itself): the degree's terms
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) {
       const int n = 16 * ct + c, base = (GS < NS) ? (n / GS) * GS : 0;
       float deg = 0.0f;
 #pragma unroll
-      for (int j = 0; j < GS; ++j)
-        if (j < N) deg = deg + (base + j == n ? 1.0f : (float)in_mult<NS, GS>(base + j, n, N, graph, sm, dense, d.gid));
+      for (int j = 0; j < GS; ++j) {
+        wl[ct][j] = base + j == n ? 1.0f : (float)in_mult<NS, GS>(base + j, n, N, graph, sm, dense, d.gid);
+        if (j < N) deg = deg + wl[ct][j];
+      }
       const int jn = (GS < NS) ? n % GS : n;
       dis[ct] = (jn < N && deg > 0.0f) ? 1.0f / sqrtf(deg) : 0.0f;
       if (n < NS && p == 0) sm.aux[n] = dis[ct];
     }
     wave_lds_sync();
+    // the lane's column picks u = 4 ks + p of (aux[u] * w(u -> n)) * dis[n]: w selected among the
+    // degree's terms of n's graph (for a slot of that graph, w(u -> n) is wl[u % GS]), aux[u] read
+    // by lane, then the products; 0 across graphs and for u or n past N, as the full table had
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) {
-      const int n = 16 * ct + c;
+      const int n = 16 * ct + c, jn = (GS < NS) ? n % GS : n, ng = (GS < NS) ? n / GS : 0;
 #pragma unroll
-      for (int u = 0; u < NS; ++u) {
-        const bool same = (GS == NS) || (u / GS == n / GS);
-        const float w = (u == n) ? 1.0f : (float)in_mult<NS, GS>(u, n, N, graph, sm, dense, d.gid);
-        const int ju = (GS < NS) ? u % GS : u, jn = (GS < NS) ? n % GS : n;
-        F.cf[ct][u] = (same && ju < N && jn < N) ? (sm.aux[u] * w) * dis[ct] : 0.0f;
+      for (int ks = 0; ks < NS / 4; ++ks) {
+        const int j0 = CP::col_j(ks, 0), j1 = CP::col_j(ks, 1), j2 = CP::col_j(ks, 2), j3 = CP::col_j(ks, 3);
+        const float w = sel4(pb0, pb1, wl[ct][j0], wl[ct][j1], wl[ct][j2], wl[ct][j3]);
+        const int u = 4 * ks + p, ju = j0 + p;
+        const bool same = GS == NS || CP::col_g(ks) == ng;
+        F.cc[ct][ks] = (same && ju < N && jn < N) ? (sm.aux[u] * w) * dis[ct] : 0.0f;
       }
+      // (no row picks: they are the attention backward's, GAT only)
     }
   }
   DF_STAMP(1);
@@ -564,19 +676,26 @@ __device__ inline void dl_forward(const float* __restrict__ P, const DGeom<NS>& 
     const float4 b0 = *reinterpret_cast<const float4*>(P + L_BIAS + 4 * p);
     const float4 b1 = *reinterpret_cast<const float4*>(P + L_BIAS + 16 + 4 * p);
     const float bias[2][4] = {{b0.x, b0.y, b0.z, b0.w}, {b1.x, b1.y, b1.z, b1.w}};
+    // every column tile's chains first (each keeps its k order), then the epilogues: the T-row
+    // store's test does not stand between two tiles' MFMAs
+    f32x4 o0[CT], o1[CT];
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) {
-      f32x4 o0 = {0.f, 0.f, 0.f, 0.f}, o1 = {0.f, 0.f, 0.f, 0.f};
+      o0[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+      o1[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int ks = 0; ks < NS / 4; ++ks) {
-        const float b = pick4(F.cf[ct], ks, p);
-        o0 = mfma16(ah[0][ks], b, o0);
-        o1 = mfma16(ah[1][ks], b, o1);
+        const float b = F.cc[ct][ks];
+        o0[ct] = mfma16(ah[0][ks], b, o0[ct]);
+        o1[ct] = mfma16(ah[1][ks], b, o1[ct]);
       }
+    }
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        F.t[ct][0][r] = tanh_fast(o0[r] + bias[0][r]);
-        F.t[ct][1][r] = tanh_fast(o1[r] + bias[1][r]);
+        F.t[ct][0][r] = tanh_fast(o0[ct][r] + bias[0][r]);
+        F.t[ct][1][r] = tanh_fast(o1[ct][r] + bias[1][r]);
       }
       const int n = 16 * ct + c;
       if (keep_tr && n < NS) {

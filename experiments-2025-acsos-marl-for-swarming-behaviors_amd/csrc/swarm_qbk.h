@@ -92,7 +92,7 @@ __device__ __forceinline__ void qbk_body(QbSmem<NS>& L, const int vb, const QbAr
   pon.store(L.Pon, threadIdx.x);
   __syncthreads();   // weight image
 
-  dl_forward<NS, -1, GS>(P, d, N, graph, A.k, A.radius, conv, A.mult, V, true, F);
+  dl_forward<NS, -1, GS, spec_complete_graph(SPEC)>(P, d, N, graph, A.k, A.radius, conv, A.mult, V, true, F);
 
   // ---- dR = W2^T dq (actions in order), dZ = dR * [z > 0]; the block's images of this wave's rows
   float dz[CT][2][4];
@@ -118,7 +118,7 @@ __device__ __forceinline__ void qbk_body(QbSmem<NS>& L, const int vb, const QbAr
     TB.X[row][p] = F.x[ct][0];
     TB.X[row][4 + p] = F.x[ct][1];
 #pragma unroll
-    for (int j = 0; j < NS / 4; ++j) TB.cm[row][4 * j + p] = pick4(F.cf[ct], j, p);
+    for (int j = 0; j < NS / 4; ++j) TB.cm[row][4 * j + p] = F.cc[ct][j];
     if (p == 0) {
       TB.X[row][8] = 0.0f;
       *reinterpret_cast<float4*>(&L.DQ[row][0]) = make_float4(dqv[ct][0], dqv[ct][1], dqv[ct][2], dqv[ct][3]);

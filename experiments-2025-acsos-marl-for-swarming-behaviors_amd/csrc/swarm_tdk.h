@@ -362,7 +362,7 @@ __device__ __forceinline__ void td_body(TdSmem<NS>& L, const int vb, const int32
   // ---- forwards: online on s (activations kept), target on s' (train_gcn_dqn.py:119-121).
   //      Everything after B1 waits for the target waves' y, so they issue first.
   if (!online && !waited) __builtin_amdgcn_s_setprio(2);
-  dl_forward<NS, 16, GS>(online ? Pon : Ptg, d, N, graph, A.k, A.radius, conv, nullptr, V, online, F);
+  dl_forward<NS, 16, GS, spec_complete_graph(SPEC)>(online ? Pon : Ptg, d, N, graph, A.k, A.radius, conv, nullptr, V, online, F);
   // fused: the rest of this tick's transitions, each as late as its first use: a for the online
   // waves' pre path here; r (published after the acting wave's reward) by the online waves after
   // it, in their wait for the target waves' y, so no poll sits between the target forward and B1
@@ -495,7 +495,7 @@ __device__ __forceinline__ void td_body(TdSmem<NS>& L, const int vb, const int32
       TB.X[row][p] = F.x[ct][0];
       TB.X[row][4 + p] = F.x[ct][1];
 #pragma unroll
-      for (int j = 0; j < NS / 4; ++j) TB.cm[row][4 * j + p] = pick4(F.cf[ct], j, p);
+      for (int j = 0; j < NS / 4; ++j) TB.cm[row][4 * j + p] = F.cc[ct][j];
       if (p == 0) { TB.X[row][8] = 0.0f; TB.gq[row] = gq; TB.d2[row] = delta * delta; }
       if (pre) {   // the pre path's images scaled by this node's gq (rows free since B1)
         float o[2][4];
