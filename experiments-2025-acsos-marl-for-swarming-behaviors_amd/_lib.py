@@ -74,6 +74,19 @@ class SwarmPopActor(ctypes.Structure):
                 ("tick0", c_uint32), ("eps", c_float)]
 
 
+PBT_F_LR, PBT_F_GAMMA = 1, 2   # swarm_pbt_cfg.fields
+PBT_MAX_MEMBERS = 1024         # SWARM_PBT_MAX_MEMBERS
+STREAM_PBT = 5                 # third Philox counter word of the PBT draws (csrc/swarm_pbt.h)
+
+
+class SwarmPbtCfg(ctypes.Structure):
+    """One PBT round (swarm_pbt_cfg): the Philox key and round of its draws, how many members are
+    replaced, which hyper-parameters a child perturbs, the two factors and the clamps."""
+    _fields_ = [("seed", c_uint64), ("round", c_uint32), ("n_replace", c_int32), ("fields", c_int32),
+                ("perturb_lo", c_float), ("perturb_hi", c_float), ("gamma_min", c_float), ("gamma_max", c_float),
+                ("lr_min", ctypes.c_double), ("lr_max", ctypes.c_double)]
+
+
 PEER_MAX = 8
 PEER_HANDLE_BYTES = 64
 PEER_SEQ_WORDS = 256
@@ -145,6 +158,8 @@ _PROTOS = {
                                               c_int32, c_stream]),
     # (cfg, actors table [P] of SwarmPopActor in device memory, P, n_ticks, stream)
     "swarm_pop_rollout": (c_int32, [POINTER(SwarmConfig), c_void_p, c_int32, c_int32, c_stream]),
+    # (pbt, score [P] float, member_hp table, members table, P, parent [P] int32: all device memory; stream)
+    "swarm_pop_exploit": (c_int32, [POINTER(SwarmPbtCfg), c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_stream]),
     "swarm_peer_buffer_bytes": (c_int64, []),
     "swarm_peer_alloc": (c_int32, [POINTER(c_void_p)]),
     "swarm_peer_free": (c_int32, [c_void_p]),

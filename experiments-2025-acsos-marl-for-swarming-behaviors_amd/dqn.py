@@ -16,6 +16,14 @@ default to the training graph), one row per evaluation in ``trainer.eval_rows`` 
 ``experiment_{experiment}-seed_{seed}-eval.csv``.  A ``PopulationTrainer`` evaluates all its
 members in one launch (``SwarmPopulation.evaluate``).  Training itself keeps every bit.
 
+Optional population-based training (``PopulationTrainer`` only): with ``config["pbt_every"] = K`` (a
+multiple of ``eval_every``) the evaluation of every K-th episode is followed by one
+``SwarmPopulation.exploit`` round: the score is each member's evaluation reward summed over envs and
+agents, formed on the device, ``round`` counts the rounds from 0 and ``config.get("pbt", {})`` holds
+``exploit``'s other keywords.  Each trainer keeps ``pbt_rows`` (episode, parent, lr, gamma after the
+round), written as ``experiment_{experiment}-seed_{seed}-pbt.csv``.  Without ``pbt_every`` nothing
+changes: the same launches, files and bits.
+
 Deliberate, documented differences (SURVEY §7 "RNG", "Vectorisation fixes"):
 random draws come from Philox keyed by (seed, tick, env), not Python ``random``;
 with ``num_envs`` > 1 each env draws its own exploration coin.
@@ -132,6 +140,7 @@ class DQNTrainer:
         self.rewards_buffer = []
         self.obstacle_hits_buffer = []
         self.eval_rows = []     # (episode, mean reward per tick, hits, final distance) per evaluation
+        self.pbt_rows = []      # (episode, parent member, lr, gamma after the round) per PBT round
         self._eval_engine = None
 
     def create_graph_from_observations(self, observations) -> Data:
@@ -209,6 +218,14 @@ class DQNTrainer:
             w.writerow(["Episode", "Reward", "Collisions", "Distance (end)"])
             w.writerows(self.eval_rows)
 
+    def save_pbt_to_csv(self):
+        os.makedirs(self.stats_path, exist_ok=True)
+        with open(f"{self.stats_path}/experiment_{self.experiment}-seed_{self.seed}-pbt.csv", mode="w",
+                  newline="") as f:
+            w = csv.writer(f)
+            w.writerow(["Episode", "Parent", "lr", "gamma"])
+            w.writerows(self.pbt_rows)
+
     def save_metrics_to_csv(self):
         os.makedirs(self.stats_path, exist_ok=True)
         with open(f"{self.stats_path}/experiment_{self.experiment}-seed_{self.seed}.csv", mode="w", newline="") as f:
@@ -268,8 +285,21 @@ class PopulationTrainer:
         """Every member's evaluation in one launch (DQNTrainer._evaluate's rows, member by member)"""
         res = self.population.evaluate(ev["envs"], n_ticks, seed=ev["seed"], episode=0, graph=ev["graph"],
                                        knn_k=ev["knn_k"])
+        self._eval_reward = res["reward"]   # [P, envs, N] on the device: what a PBT round scores
         res = {k: v.cpu() for k, v in res.items()}
         return [{k: v[m] for k, v in res.items()} for m in range(self.population.P)]
+
+    def _pbt_round(self, episode: int, rnd: int, kw: dict):
+        """One exploit round scored by the evaluation just run: each member's reward summed over
+        envs and agents, on the device.  One row per trainer: who it now descends from and the lr
+        and gamma it goes on with."""
+        pop = self.population
+        score = self._eval_reward.sum(dim=(1, 2))
+        parent = pop.exploit(score, round=rnd, **kw).tolist()
+        if pop._hp_stale:   # kw asked for sync=False: the rows below and the final flush need the host hp
+            pop.sync_hp()
+        for m, t in enumerate(self.trainers):
+            t.pbt_rows.append((episode, parent[m], t.engine.hp.lr_d, t.engine.hp.gamma))
 
     def train_model(self, config):
         _train_loop(self, self.population, self.trainers, (self.population.P,), config, "Seed {seed}, ",
@@ -287,6 +317,21 @@ def eval_row(episode: int, res: dict, n_ticks: int) -> tuple:
     mean over the evaluation environments."""
     return (episode, float(res["reward"].sum(dim=1).mean()) / max(n_ticks, 1), float(res["hits"].mean()),
             float(res["avg_dist"].mean()))
+
+
+def pbt_schedule(config):
+    """``config["pbt_every"]`` checked: None (no PBT) or an integer >= 1 that ``eval_every`` divides
+    (a round is scored by the evaluation that precedes it)."""
+    every = config.get("pbt_every")
+    if every is None:
+        return None
+    if isinstance(every, bool) or int(every) != every or every < 1:
+        raise ValueError(f"pbt_every must be an integer >= 1 or None, not {every!r}")
+    eval_every = config.get("eval_every")
+    if eval_every is None or isinstance(eval_every, bool) or eval_every < 1 or every % eval_every != 0:
+        raise ValueError(f"pbt_every = {every!r} needs eval_every to divide it (eval_every = {eval_every!r}): a PBT "
+                         "round is scored by the evaluation of its episode")
+    return int(every)
 
 
 def _train_loop(driver, group, trainers, shape, config, prefix: str, saved: str):
@@ -312,6 +357,11 @@ def _train_loop(driver, group, trainers, shape, config, prefix: str, saved: str)
         raise ValueError(f"eval_every must be an integer >= 1 or None, not {eval_every!r}")
     ev = dict(envs=config.get("eval_envs", 8), seed=config.get("eval_seed", 6967), graph=config.get("eval_graph"),
               knn_k=config.get("eval_knn_k"))
+    pbt_every = pbt_schedule(config)
+    if pbt_every is not None:
+        if not hasattr(driver, "_pbt_round"):
+            raise ValueError("pbt_every needs a PopulationTrainer: a lone trainer has nobody to exploit")
+        group.per_member_hp = True   # before the episode is captured: the rows will change
     epsilon = initial_epsilon
     driver._acc_reward = torch.zeros(shape, device=group.device)
     driver._acc_loss = torch.zeros(shape, device=group.device)
@@ -361,6 +411,8 @@ def _train_loop(driver, group, trainers, shape, config, prefix: str, saved: str)
         if eval_every is not None and (episode + 1) % eval_every == 0:
             for t, res in zip(trainers, driver._evaluate(ev, max_steps)):
                 t.eval_rows.append(eval_row(episode, res, max_steps))
+        if pbt_every is not None and (episode + 1) % pbt_every == 0:
+            driver._pbt_round(episode, (episode + 1) // pbt_every - 1, dict(config.get("pbt", {})))
     print("Training completed")
     for t in trainers:
         t._sync_models()
@@ -369,6 +421,8 @@ def _train_loop(driver, group, trainers, shape, config, prefix: str, saved: str)
         t.save_metrics_to_csv()
         if eval_every is not None:
             t.save_eval_to_csv()
+        if pbt_every is not None:
+            t.save_pbt_to_csv()
     print(saved)
 
 

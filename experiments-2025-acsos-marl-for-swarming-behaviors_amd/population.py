@@ -24,10 +24,16 @@ Evaluation has the same shape (1-8 environments per policy, one or two blocks pe
 ``ActorPopulation`` rolls out P existing engines in one swarm_pop_rollout launch, grid
 (ceil(B / 4), P), and ``SwarmPopulation.evaluate`` runs every member's current weights on one set
 of evaluation environments that way (tests/test_gpu_pop_rollout.py).
+
+Population-based training closes the loop on the device: ``SwarmPopulation.exploit(score, ...)``
+(swarm_pop_exploit) ranks the members by a device score, copies the best members' learners,
+optimizer state and hyper-parameter rows over the worst and perturbs the copies' lr / gamma, in two
+launches with no host round trip (tests/test_gpu_pop_pbt.py).
 """
 from __future__ import annotations
 
 import ctypes
+import math
 from typing import Sequence
 
 import torch
@@ -72,6 +78,56 @@ def member_hp_kwargs(P: int, engine_kwargs: dict) -> list:
                 kw[k] = tuple(kw[k])
             check_hp_values(**{k: kw[k]})
     return per_member
+
+
+def _take_row(hp: SwarmAdamCfg, row: SwarmAdamCfg):
+    """what a member's row decides (take_member_hp, csrc/swarm_popk.h): hp keeps its batch,
+    world_size and flags"""
+    for k in ("lr", "beta1", "beta2", "eps", "max_norm", "gamma", "update_target_every", "lr_d", "beta1_d", "beta2_d"):
+        setattr(hp, k, getattr(row, k))
+
+
+PBT_FIELDS = {"lr": _lib.PBT_F_LR, "gamma": _lib.PBT_F_GAMMA}
+
+
+def pbt_round_cfg(P: int, score, device, *, round: int, seed: int = 0, frac: float = 0.25, perturb=(0.8, 1.2),
+                  fields=("lr",), lr_bounds=(1e-6, 1e-1), gamma_bounds=(0.0, 0.9999)) -> _lib.SwarmPbtCfg:
+    """``SwarmPopulation.exploit``'s arguments checked (ValueError; nothing is launched) and packed
+    into the swarm_pbt_cfg of one round for a population of P members on ``device``."""
+    if P > _lib.PBT_MAX_MEMBERS:
+        raise ValueError(f"exploit: {P} members, at most {_lib.PBT_MAX_MEMBERS}")
+    if not (isinstance(score, torch.Tensor) and score.dtype == torch.float32 and tuple(score.shape) == (P,)
+            and score.device == torch.device(device) and score.is_contiguous()):
+        raise ValueError(f"score: a contiguous float32 tensor of shape [{P}] on {device}")
+    if isinstance(round, bool) or not isinstance(round, int) or not 0 <= round < 1 << 32:
+        raise ValueError(f"round must be an integer in [0, 2^32), not {round!r}")
+    if isinstance(seed, bool) or not isinstance(seed, int):
+        raise ValueError(f"seed must be an integer, not {seed!r}")
+    if not _is_real(frac) or not 0.0 <= frac <= 0.5:
+        raise ValueError(f"frac must lie in [0, 0.5] (parents and children are disjoint sets), not {frac!r}")
+    if isinstance(fields, str):
+        fields = (fields,)
+    unknown = [f for f in fields if f not in PBT_FIELDS]
+    if unknown:
+        raise ValueError(f"fields: {unknown!r} cannot be perturbed ({', '.join(PBT_FIELDS)})")
+    for name, pair, low_ok in (("perturb", perturb, False), ("lr_bounds", lr_bounds, False),
+                               ("gamma_bounds", gamma_bounds, True)):
+        if not (_is_pair(pair) and all(_is_real(v) for v in pair)):
+            raise ValueError(f"{name} must be a pair of finite numbers, not {pair!r}")
+        if not pair[0] <= pair[1] or not (low_ok or pair[0] > 0):
+            raise ValueError(f"{name} must be in order{'' if low_ok else ' and > 0'}, not {pair!r}")
+    bits = 0
+    for f in fields:
+        bits |= PBT_FIELDS[f]
+    pbt = _lib.SwarmPbtCfg(seed & 0xFFFFFFFFFFFFFFFF, round, int(frac * P), bits, perturb[0], perturb[1],
+                           gamma_bounds[0], gamma_bounds[1], float(lr_bounds[0]), float(lr_bounds[1]))
+    if not (pbt.perturb_lo > 0 and math.isfinite(pbt.perturb_hi)):   # as rounded to fp32
+        raise ValueError(f"perturb must be a pair of finite fp32 numbers > 0, not {perturb!r}")
+    return pbt
+
+
+def _is_real(v) -> bool:
+    return isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v)
 
 
 class SwarmPopulation:
@@ -154,6 +210,10 @@ class SwarmPopulation:
         self._hp_table = torch.frombuffer(bytearray(_bytes_of(rows)), dtype=torch.uint8).to(dev).view(P, -1)
         self.per_member_hp = self._rows_differ()
         self._evals = {}   # evaluate(): (n_envs, graph, knn_k) -> its launches, start and state rows
+        # exploit(): each member's parent of the last PBT round; the device table's rows are ahead
+        # of the members' host hp after an exploit(sync=False), until sync_hp()
+        self.parent = torch.arange(P, dtype=torch.int32, device=dev)
+        self._hp_stale = False
 
     @staticmethod
     def _row(e) -> SwarmAdamCfg:
@@ -203,6 +263,8 @@ class SwarmPopulation:
         ``per_member_hp = True`` before capturing a population whose rows will change)."""
         if not 0 <= m < self.P:
             raise ValueError(f"member {m} of {self.P}")
+        if self._hp_stale:   # the row is rewritten whole from the member's host hp
+            self.sync_hp()
         e = self.members[m]
         e.set_hp(**fields)   # validates
         row = torch.frombuffer(bytearray(_bytes_of(self._row(e))), dtype=torch.uint8)
@@ -212,6 +274,54 @@ class SwarmPopulation:
             self.hp = _copy_of(e.hp)
             self.hp.flags = flags
         self.per_member_hp = self.per_member_hp or self._rows_differ()
+
+    # ------------------------------------------------------------------ population-based training
+    def exploit(self, score, *, round: int, seed: int = 0, frac: float = 0.25, perturb=(0.8, 1.2), fields=("lr",),
+                lr_bounds=(1e-6, 1e-1), gamma_bounds=(0.0, 0.9999), sync: bool = True):
+        """One round of population-based training on the device (swarm_pop_exploit: two launches, no
+        host round trip).  ``score`` is a [P] float32 tensor on the population's device, higher is
+        better (NaN is worst).  The ``n_replace = int(frac * P)`` worst members (0 <= frac <= 0.5)
+        each take over one of the n_replace best: the seven learner rows, the gradient with a
+        pending step, the optimizer's control words and the hyper-parameter row; then the child's
+        ``fields`` ("lr", "gamma") are multiplied by one of the two ``perturb`` factors (gamma as
+        1 - (1 - gamma) * f) and clamped to their bounds.  A child keeps its own tick, ring, env
+        state, eps and Philox streams; parents and the members in between are not written.  The
+        draws are Philox blocks keyed (``seed``, ``round``, member): a round is reproducible, and a
+        new ``round`` draws anew.  Returns ``parent``, a device int32 [P] (the population's own
+        buffer; parent[m] == m for every member that was not replaced).
+
+        It sets ``per_member_hp = True`` before the call: the children's rows now differ.  The
+        table is read on every launch, so a hipGraph captured while ``per_member_hp`` was True sees
+        the new rows at its next replay; one captured while it was False holds the shared hp as a
+        kernel argument and does not (set ``per_member_hp = True`` before capturing a population
+        that will be exploited).  ``round`` is a kernel argument: a captured exploit replays the
+        same round.
+
+        ``sync=True`` ends with ``sync_hp()`` (one device read).  With ``sync=False`` nothing is
+        read back (the call can be captured) and the members' host ``hp`` lag behind the device
+        rows until ``sync_hp()``; ``flush`` and ``set_member_hp`` call it first when needed.
+        Arguments are checked (ValueError) before anything is launched."""
+        pbt = pbt_round_cfg(self.P, score, self.device, round=round, seed=seed, frac=frac, perturb=perturb,
+                            fields=fields, lr_bounds=lr_bounds, gamma_bounds=gamma_bounds)
+        self.per_member_hp = True
+        call(self.lib, "swarm_pop_exploit", pbt, ptr(score), ptr(self._hp_table), ptr(self._table_min), self.P,
+             ptr(self.parent))
+        self._hp_stale = pbt.n_replace > 0
+        if sync:
+            self.sync_hp()
+        return self.parent
+
+    def sync_hp(self):
+        """Bring every ``members[m].hp`` and the shared ``hp`` (which follows member 0) in line with
+        the device row table: one device read.  Each keeps its own batch, world_size and flags
+        (a row's are ignored by the kernels).  Needed after ``exploit(sync=False)`` before a
+        member's host hp is passed to the library (a member's own ``flush``)."""
+        rows = self._hp_table.cpu().numpy().tobytes()
+        n = ctypes.sizeof(SwarmAdamCfg)
+        for m, e in enumerate(self.members):
+            _take_row(e.hp, SwarmAdamCfg.from_buffer_copy(rows[m * n:(m + 1) * n]))
+        _take_row(self.hp, self.members[0].hp)
+        self._hp_stale = False
 
     def reset(self, episode=None):
         """Reset every member's environments (one small launch per member, once per episode)."""
@@ -231,6 +341,8 @@ class SwarmPopulation:
 
     def flush(self):
         """Apply every member's pending optimizer step (one small launch per member)."""
+        if self._hp_stale:   # swarm_adam_flush takes each member's host hp
+            self.sync_hp()
         for e in self.members:
             e.flush()
 

@@ -434,6 +434,59 @@ typedef struct swarm_pop_actor {
 int swarm_pop_rollout(const swarm_config* cfg, const swarm_pop_actor* actors, int32_t n_actors,
                       int32_t n_ticks, void* stream);
 
+/* ---- Population-based training (Jaderberg et al. 2017): exploit and explore on the device.  The
+ * reference trains every seed under fixed hyper-parameters and never moves a learner
+ * (train_gcn_dqn.py:85,112-137,262-290); this works on the tables of swarm_pop_train_tick_hp.
+ * The n_replace worst members (children) each take over the learner, the optimizer state and the
+ * hyper-parameter row of one of the n_replace best (parents) and perturb lr and / or gamma.
+ *
+ * score [n_members] floats, higher is better; parent [n_members] int32 (output); member_hp and
+ * members as swarm_pop_train_tick_hp takes them.  All four are DEVICE memory.
+ *
+ * Ranking: rank(m) = #{ j : s_j > s_m, or s_j == s_m and j < m }, a NaN score counting as -inf
+ * (NaN members are worst; among equals the lower index ranks better).  Parents are ranks
+ * 0 .. n_replace-1, children ranks n_members-n_replace .. n_members-1; n_replace <= n_members / 2
+ * keeps the two sets disjoint, so nothing that is written is read by anyone else.
+ * Draws: child m draws one block w = philox4x32(round, m, 5, 0, k0, k1) (stream id 5; k0 / k1 the
+ * low / high word of seed).  parent[m] = the member of rank (w.x * n_replace) >> 32; the lr factor
+ * is perturb_lo if (w.y >> 8) * 2^-24 < 0.5f, else perturb_hi; the gamma factor likewise from w.z.
+ * Every other member gets parent[m] = m and is not written at all.
+ * Copy, parent p -> child c, through the descriptors' pointers: the seven learner rows
+ * (swarm_n_params() floats each), lr.grad (SWARM_GRAD_FLOATS floats: a pending step of the child
+ * is then the parent's pending step) and the control words of the optimizer: adam_step, loss,
+ * grad_norm, trained, beta_pow[4], adam_step_size, adam_inv_bc2, one_m_beta1, one_m_beta2.  The
+ * child keeps everything else: tick, write_slot, filled_slots, eps, episode, the sampling-key
+ * cache, peer_hold, its ring, env state, workspace, slabs and outputs.
+ * Explore: row c of member_hp becomes row p, then
+ *   SWARM_PBT_F_LR   : lr_d = min(max(lr_d_p * (double)f, lr_min), lr_max), with (double)lr_p in
+ *                      place of lr_d_p where lr_d_p == 0; lr = (float)lr_d;
+ *   SWARM_PBT_F_GAMMA: gamma = min(max(1.0f - (1.0f - gamma_p) * f, gamma_min), gamma_max), fp32.
+ * That is "load the parent's optimizer state, then rewrite the child's row": the control block's
+ * next-step scalars are the parent's, so the new lr acts one optimizer step later.
+ *
+ * Checks, in this order, before any launch: a NULL pbt, score, member_hp, members or parent:
+ * SWARM_E_BADARG; n_members < 1: SWARM_E_BADARG; n_members > SWARM_PBT_MAX_MEMBERS:
+ * SWARM_E_UNSUPPORTED; n_replace outside [0, n_members / 2]: SWARM_E_BADARG; unknown fields bits:
+ * SWARM_E_BADARG; then SWARM_E_BADARG unless perturb_lo, perturb_hi are finite, > 0 and
+ * lo <= hi, gamma_min <= gamma_max are finite, and 0 < lr_min <= lr_max are finite.
+ * n_replace == 0 launches only the kernel that writes parent[m] = m.  Two launches otherwise, no
+ * allocation, no host sync: capturable (round is a kernel argument: frozen into a hipGraph).
+ * (tests/test_gpu_pop_pbt.py) */
+#define SWARM_PBT_F_LR 1
+#define SWARM_PBT_F_GAMMA 2
+#define SWARM_PBT_MAX_MEMBERS 1024
+typedef struct swarm_pbt_cfg {
+  uint64_t seed;        /* Philox key of the PBT stream, split into k0/k1 as swarm_config.seed is */
+  uint32_t round;       /* PBT round number: first counter word */
+  int32_t n_replace;    /* members replaced = parents' pool size; 0 <= n_replace <= n_members / 2 */
+  int32_t fields;       /* SWARM_PBT_F_*: which hyper-parameters a child perturbs */
+  float perturb_lo, perturb_hi;       /* the two factors, e.g. 0.8f, 1.2f; finite, > 0 */
+  float gamma_min, gamma_max;         /* clamp of the child's gamma */
+  double lr_min, lr_max;              /* clamp of the child's lr_d */
+} swarm_pbt_cfg;
+int swarm_pop_exploit(const swarm_pbt_cfg* pbt, const float* score, swarm_adam_cfg* member_hp,
+                      const swarm_pop_member* members, int32_t n_members, int32_t* parent, void* stream);
+
 /* Workspace (floats) of swarm_td_grad's per-block gradient slabs. */
 int64_t swarm_td_workspace_floats(const swarm_config* cfg, int32_t batch);
 

@@ -22,7 +22,20 @@ Same method: HIP events around back-to-back replays, the ways alternating, media
 max, here in us per evaluation of all P policies (one 100-tick rollout each).  The states are not
 reset between replays (both ways advance theirs alike).
 
-usage: python tools/pop_time.py [--rollout] [--repeats 7] [--sizes 1,10,64] [--out population_time.json]
+``--pbt`` times one round of population-based training at the reference's shape (1 env, batch 32),
+P learners that have trained for 40 ticks, frac = 0.25, lr and gamma perturbed, a fixed device score:
+  exploit_graph : `rounds` calls of SwarmPopulation.exploit(sync=False) (swarm_pop_exploit: the plan
+               and the copy launch, nothing read back) captured into one hipGraph, replayed: the
+               device time of a round;
+  exploit_eager : the same calls issued eagerly, back to back: what a round costs a Python caller;
+  host        : the same round done with what the population offered before swarm_pop_exploit: a
+               host read of the scores, the ranking on the host, per replaced member tensor copies
+               of the same buffers (seven learner rows, grad, the optimizer's control words) and a
+               set_member_hp.
+Same method: HIP events around back-to-back rounds, the ways alternating, medians with min and max,
+in us per round.  Default sizes 10,64.
+
+usage: python tools/pop_time.py [--rollout | --pbt] [--repeats 7] [--sizes 1,10,64] [--out population_time.json]
 Prints one JSON line per configuration and population size.
 """
 import argparse
@@ -151,19 +164,104 @@ def measure_rollout(scen, N, P, repeats, n_envs=8, knn_k=5):
     return out
 
 
+PBT_ROUNDS = 50
+PBT_CTRL_WORDS = [3, 5, 6, 7, 10, 11, 12, 13, 14, 15, 24, 25]   # what swarm_pop_exploit copies of swarm_ctrl
+
+
+def measure_pbt(scen, N, P, repeats):
+    kw = dict(scenario=scen, n_agents=N, n_envs=1, batch=32, eps=0.05, shared_reset=True)
+    pops = {}
+    for way in ("exploit_graph", "exploit_eager", "host"):
+        pop = pops[way] = swarm_amd.SwarmPopulation(seeds=list(range(P)), **kw)
+        pop.per_member_hp = True
+        pop.reset(0)
+        for _ in range(40):   # past the batch size: moments, a pending step
+            pop.train_tick()
+    dev = pops["host"].device
+    score = torch.randn(P, generator=torch.Generator().manual_seed(5)).to(dev)
+    pbt = dict(frac=0.25, fields=("lr", "gamma"), seed=1)
+    n_replace = int(pbt["frac"] * P)
+
+    def device_rounds(pop):
+        for r in range(PBT_ROUNDS):
+            pop.exploit(score, round=r, sync=False, **pbt)
+
+    def host_round(pop, r):
+        s = score.tolist()   # the host read
+        order = sorted(range(P), key=lambda m: (-s[m], m))
+        for i, c in enumerate(order[P - n_replace:]):
+            p = order[(i + r) % n_replace]
+            ce, pe = pop.members[c], pop.members[p]
+            ce._lrn[:, :L.N_PARAMS].copy_(pe._lrn[:, :L.N_PARAMS])
+            ce.grad.copy_(pe.grad)
+            ce.ctrl[PBT_CTRL_WORDS] = pe.ctrl[PBT_CTRL_WORDS]
+            f = 0.8 if (i + r) % 2 else 1.2
+            pop.set_member_hp(c, lr=min(max(pe.hp.lr_d * f, 1e-6), 1e-1),
+                              gamma=min(max(1.0 - (1.0 - pe.hp.gamma) * f, 0.0), 0.9999),
+                              betas=(pe.hp.beta1_d, pe.hp.beta2_d), adam_eps=pe.hp.eps, max_norm=pe.hp.max_norm,
+                              update_target_every=pe.hp.update_target_every)
+
+    def host_rounds():
+        for r in range(PBT_ROUNDS):
+            host_round(pops["host"], r)
+
+    graph = swarm_amd.engine.capture_ticks(dev, 1, lambda: device_rounds(pops["exploit_graph"]))
+    ways = {"exploit_graph": graph.replay, "exploit_eager": lambda: device_rounds(pops["exploit_eager"]),
+            "host": host_rounds}
+    # chains of PBT_ROUNDS rounds per window: enough that a window lasts tens of milliseconds
+    windows = {"exploit_graph": 200, "exploit_eager": 50, "host": max(1, 40 // P)}
+
+    def window(k):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(windows[k]):
+            ways[k]()
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b) * 1e3 / (windows[k] * PBT_ROUNDS)
+
+    for k in ways:
+        window(k)
+    times = {k: [] for k in ways}
+    for _ in range(repeats):
+        for k in ways:
+            times[k].append(window(k))
+    torch.cuda.synchronize()
+    for pop in pops.values():   # the populations still train after all those rounds
+        pop.sync_hp()
+        pop.train_tick()
+        pop.check_handoffs()
+        assert all(math.isfinite(c["loss"]) for c in pop.read_ctrl())
+    assert int((pops["exploit_graph"].parent != torch.arange(P, device=dev)).sum()) == n_replace
+    out = {"mode": "pbt", "scenario": scen, "n_agents": N, "n_envs": 1, "batch": 32, "population": P,
+           "n_replace": n_replace, "rounds_per_chain": PBT_ROUNDS, "chains_per_window": windows, "repeats": repeats,
+           "build": pops["host"].lib.swarm_build_info().decode()}
+    for k, v in times.items():
+        out[k + "_us_per_round"] = round(statistics.median(v), 3)
+        out[k + "_us_min_max"] = [round(min(v), 3), round(max(v), 3)]
+    out["host_over_exploit_eager"] = round(out["host_us_per_round"] / out["exploit_eager_us_per_round"], 2)
+    out["host_over_exploit_graph"] = round(out["host_us_per_round"] / out["exploit_graph_us_per_round"], 2)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--rollout", action="store_true", help="time evaluation rollouts instead of training ticks")
+    ap.add_argument("--pbt", action="store_true", help="time one PBT round: swarm_pop_exploit against host copies")
     ap.add_argument("--repeats", type=int, default=7)
-    ap.add_argument("--sizes", default="1,10,64")
+    ap.add_argument("--sizes", default=None, help="population sizes (default 1,10,64; --pbt: 10,64)")
     ap.add_argument("--configs", default=None, help="e.g. GoTo:5,ObstacleAvoidance:10 (default: all four)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    a.sizes = a.sizes or ("10,64" if a.pbt else "1,10,64")
+    if a.pbt and not a.configs:
+        a.configs = "GoTo:5"
+    fn = measure_pbt if a.pbt else measure_rollout if a.rollout else measure
     configs = CONFIGS if not a.configs else tuple((c.split(":")[0], int(c.split(":")[1])) for c in a.configs.split(","))
     rows = []
     for scen, N in configs:
         for P in [int(x) for x in a.sizes.split(",")]:
-            rows.append((measure_rollout if a.rollout else measure)(scen, N, P, a.repeats))
+            rows.append(fn(scen, N, P, a.repeats))
             print(json.dumps(rows[-1]), flush=True)
             if a.out:
                 os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
