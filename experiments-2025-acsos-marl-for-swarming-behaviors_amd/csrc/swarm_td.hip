@@ -93,6 +93,10 @@ __global__ __launch_bounds__(kAdamNT) void adam_kernel(AdamArgs A) {
       ctrl_set_double(C, CTRL_B1POW, ctrl_get_double(C, CTRL_B1POW) * adam_beta1(A.hp));
       ctrl_set_double(C, CTRL_B2POW, ctrl_get_double(C, CTRL_B2POW) * adam_beta2(A.hp));
       ctrl_store_next_scalars(C, A.hp);
+      // (float)(1 - beta) of the next step from this launch's hp, as red_control rewrites it every
+      // fused tick: after set_hp(betas=...) the old values act for this one step only, on every path
+      C->one_m_beta1 = (float)(1.0 - adam_beta1(A.hp));
+      C->one_m_beta2 = (float)(1.0 - adam_beta2(A.hp));
     }
     if (A.flush) {
       C->trained = 0u;

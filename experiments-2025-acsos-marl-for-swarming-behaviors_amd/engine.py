@@ -210,9 +210,21 @@ class SwarmEngine:
         """Change optimizer hyper-parameters (``HP_FIELDS``: lr, gamma, betas, adam_eps, max_norm,
         update_target_every) for the launches that follow.  ``hp`` is a kernel argument of every
         launch, so eager calls see the new values at once and a hipGraph captured before keeps
-        the old ones.  The control block holds the next optimizer step's Adam scalars, formed
-        from the hp of the launch that wrote them: a new lr (or beta) acts one optimizer step
-        later.  ``SwarmPopulation.set_member_hp`` is defined by this method."""
+        the old ones.  An optimizer step computes with the hp of the launch that applies it: the
+        fused ticks apply tick t's step in tick t + 1's launch (or in ``flush``), ``adam`` applies
+        it at once, so a change after tick t reaches tick t's step on the fused paths only.
+
+        ``gamma`` and ``update_target_every`` act at once.  So do ``adam_eps``, ``max_norm`` and
+        the factor beta2 that v decays by.  The control block holds the rest of the next step's
+        scalars, formed from the hp of the launch that applied the step before it: the step size
+        lr / (1 - beta1 product), the second bias correction and 1 - beta1, 1 - beta2.  The first
+        step applied with new values (the transition step) therefore still moves by the old lr
+        with the old bias corrections, moves m by the old beta1, and forms
+        v = new beta2 * v + (1 - old beta2) * g^2; from the step after it every value is the new
+        one, on every path alike.  The bias corrections are 1 - the product of the betas each
+        applied step carried, not 1 - beta**step: the same while the betas never change.
+        tests/test_gpu_hp_reference.py pins this step.  ``SwarmPopulation.set_member_hp`` is
+        defined by this method."""
         check_hp_values(**fields)
         hp = self.hp
         for k, v in fields.items():

@@ -92,9 +92,21 @@ typedef struct swarm_ctrl {
                              Cleared only by swarm_ctrl_init; PeerExchange.check() raises on it. */
   float one_m_beta1;      /* words 24-25: (float)(1 - beta1), (float)(1 - beta2) formed in double from   */
   float one_m_beta2;      /* swarm_adam_cfg's double betas by swarm_ctrl_init, as torch forms them, and
-                             rewritten by every swarm_reduce_advance[_peer]; swarm_adam_step / _flush
-                             form them from their swarm_adam_cfg when a word is 0 (a control block
-                             that skipped swarm_ctrl_init), so no step freezes m and v            */
+                             rewritten from the launch's swarm_adam_cfg by every
+                             swarm_reduce_advance[_peer] and by every optimizer step that
+                             swarm_adam_step / _flush apply; those two form them from their
+                             swarm_adam_cfg when a word is 0 (a control block that skipped
+                             swarm_ctrl_init), so no step freezes m and v.
+                             After a change of swarm_adam_cfg between two optimizer steps, the first
+                             step launched with the new values (the transition step, on every path
+                             alike) takes from the control block what the launch before it wrote:
+                             adam_step_size (the old lr over the old beta1's bias correction),
+                             adam_inv_bc2 and one_m_beta1/2 (the old betas); it takes eps, max_norm
+                             and v's decay factor beta2 from its own swarm_adam_cfg (the new ones).
+                             So m moves by the old beta1 and v = new beta2 * v + (1 - old beta2) g^2
+                             for that one step.  Every later step uses the new values throughout,
+                             with bias corrections 1 - (the product of the beta each launch carried),
+                             not 1 - beta^step.  gamma and update_target_every act at once.      */
   uint32_t pad1[6];
 } swarm_ctrl;           /* 32 words */
 /* A fresh control block comes from swarm_ctrl_init (all counters 0, beta powers 1). */

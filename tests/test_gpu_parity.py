@@ -580,9 +580,24 @@ def test_training_is_bitwise_deterministic(sw, golden_weights):
 def test_fused_tick_equals_unfused(sw, golden_weights, scen, N, graph, conv):
     """Fused tick (optimizer step deferred into the next act launch, ping-pong buffers)
     == act + td_grad + grad_reduce + adam_step, bit for bit, incl. target syncs."""
+    _fused_tick_equals_unfused(sw, golden_weights, scen, N, graph, conv)
+
+
+# every optimizer hyper-parameter off its default at once (tests/hp_cases.py ALL_AT_ONCE) and gamma
+OTHER_HP = dict(lr=3e-4, betas=(0.5, 0.9), adam_eps=1e-3, max_norm=0.05, update_target_every=1, gamma=0.5)
+
+
+@pytest.mark.parametrize("scen,N,graph,conv", [("GoTo", 8, "complete", "gat"), ("ObstacleAvoidance", 12, "knn", "gat")])
+def test_fused_tick_equals_unfused_at_other_hyper_parameters(sw, golden_weights, scen, N, graph, conv):
+    """The same at OTHER_HP: the paths agree where no hyper-parameter is the reference's."""
+    _fused_tick_equals_unfused(sw, golden_weights, scen, N, graph, conv, **OTHER_HP)
+
+
+def _fused_tick_equals_unfused(sw, golden_weights, scen, N, graph, conv, **hp):
     p = _params(golden_weights, "go_to" if scen == "GoTo" else "obstacle_avoidance", 4)
     kw = dict(seed=21, params=p, batch=48, eps=0.25, graph=graph, knn_k=5, update_target_every=3,
               replay_capacity=16 * 64, conv=conv)
+    kw.update(hp)
     a = sw.SwarmEngine(scen, N, 16, **kw)
     b = sw.SwarmEngine(scen, N, 16, **kw)
     a.reset(0)
@@ -623,9 +638,22 @@ def test_one_launch_tick_equals_three_launch_tick(sw, golden_weights, scen, N, c
     actions, rewards, gradient, state, replay ring, weights.  Small rings make most draws come
     from the slot being written (slots = 1: all of them; with 4096 / 2048 envs far more blocks
     than are resident, so most TD blocks start only after acting blocks have ended)."""
+    _one_launch_tick_equals_three_launch_tick(sw, golden_weights, scen, N, conv, B, slots, graph)
+
+
+@pytest.mark.parametrize("scen,N,conv,B,slots,graph", [("GoTo", 8, "gat", 64, 4, "complete"),
+                                                        ("ObstacleAvoidance", 11, "gcn", 33, 2, "knn")])
+def test_one_launch_tick_equals_three_launch_tick_at_other_hyper_parameters(sw, golden_weights, scen, N, conv, B, slots,
+                                                                            graph):
+    """The same at OTHER_HP: the paths agree where no hyper-parameter is the reference's."""
+    _one_launch_tick_equals_three_launch_tick(sw, golden_weights, scen, N, conv, B, slots, graph, **OTHER_HP)
+
+
+def _one_launch_tick_equals_three_launch_tick(sw, golden_weights, scen, N, conv, B, slots, graph, **hp):
     p = _params(golden_weights, "go_to" if scen == "GoTo" else "obstacle_avoidance", 2)
     kw = dict(seed=9, params=p, batch=B, eps=0.3, update_target_every=3, replay_capacity=slots * B, conv=conv,
               graph=graph, knn_k=5, radius=0.25)
+    kw.update(hp)
     a = sw.SwarmEngine(scen, N, B, **kw)
     b = sw.SwarmEngine(scen, N, B, **kw)
     assert a.fused
