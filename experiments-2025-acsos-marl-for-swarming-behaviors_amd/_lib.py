@@ -22,6 +22,7 @@ F_SHARED_RESET, F_RANDOM_OA = 1, 2
 N_PARAMS = 1673
 NET_GCN, NET_GAT3 = 0, 1
 GAT3_N_PARAMS = 409
+GAT3_GRAD_FLOATS = 416    # SWARM_GAT3_GRAD_FLOATS: 409 gradients, then zeros
 GRAD_FLOATS = 1792        # SWARM_GRAD_FLOATS: gradient, loss sum, the clip norm's group partials
 GRAD_SQ_BASE = 1680       # SWARM_GRAD_SQ_BASE
 ADAM_F_NORM_PARTIALS = 1  # swarm_adam_cfg.flags
@@ -122,6 +123,8 @@ _PROTOS = {
     "swarm_q_forward": (c_int32, [POINTER(SwarmConfig), c_void_p, c_void_p, c_void_p, c_void_p, c_stream]),
     "swarm_q_backward": (c_int32, [POINTER(SwarmConfig), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_stream]),
+    "swarm_gat3_q_backward": (c_int32, [POINTER(SwarmConfig), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_stream]),
     "swarm_act_step": (c_int32, [POINTER(SwarmConfig), c_void_p, c_void_p, POINTER(SwarmReplay), c_void_p,
                                  POINTER(SwarmActOut), c_stream]),
     "swarm_train_act_step": (c_int32, [POINTER(SwarmConfig), POINTER(SwarmAdamCfg), POINTER(SwarmLearner), c_void_p,
@@ -173,6 +176,10 @@ _PROTOS = {
     "swarm_host_sample_position": (c_uint32, [c_uint32, c_uint32, c_uint32, c_uint32, c_uint32]),
 }
 EXPORTED = tuple(_PROTOS)
+# added under ABI 10 after other additions: a library of an earlier build of the same ABI (the A / B
+# side of tools/bitcmp.py, SWARM_LIB_PATH) lacks it and still loads; calling it there raises.  The
+# in-tree library must have every symbol (__graft_entry__.build, tests/test_cpu_host.py).
+_NEWEST = ("swarm_gat3_q_backward",)
 
 _lib = None
 
@@ -182,6 +189,8 @@ def _open(path: str):
         raise RuntimeError(f"{os.path.basename(path)} not built at {path}; run __graft_entry__.build()")
     lib = ctypes.CDLL(path)
     for name, (res, args) in _PROTOS.items():
+        if name in _NEWEST and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

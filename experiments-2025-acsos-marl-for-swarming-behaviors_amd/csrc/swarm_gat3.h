@@ -1,7 +1,8 @@
 // swarm_gat3.h — the three-layer GAT (hidden 8) held by the reference's Flocking
-// checkpoints (data/models/experiment_Flocking-seed_*.pth: conv1..conv3, lin1, lin2),
-// forward only (acting and evaluation), one graph per wave with the D layout's lane map
-// (node n = 16 ct + c, row group p).
+// checkpoints (data/models/experiment_Flocking-seed_*.pth: conv1..conv3, lin1, lin2): the
+// forward of the acting and evaluation kernels, one graph per wave with the D layout's lane map
+// (node n = 16 ct + c, row group p).  Its backward for a caller's dL/dQ is swarm_gat3_bwd.h, with a
+// keeping forward of its own: this one is the acting kernels' code and stays as it is.
 //
 // Architecture: the GCN class with its commented layers (train_gcn_dqn.py:51-70, the
 // conv2/conv3 lines :54-55 and :65-68):

@@ -120,7 +120,8 @@ class SwarmEngine:
         sid = SCENARIOS[scenario] if isinstance(scenario, str) else int(scenario)
         flags = (_lib.F_SHARED_RESET if shared_reset else 0) | (_lib.F_RANDOM_OA if random_oa else 0)
         if net == "gat3" and learn:
-            raise ValueError("net='gat3' (the Flocking checkpoints' three-layer GAT) is forward only: use learn=False")
+            raise ValueError("net='gat3' (the Flocking checkpoints' three-layer GAT) is not trained by the engine: use "
+                             "learn=False (GAT3(autograd=True) is its differentiable class)")
         self.net = net
         self.cfg = SwarmConfig(n_envs, n_agents, sid, GRAPHS[graph], knn_k, CONVS[conv], env_offset, flags,
                                seed & 0xFFFFFFFFFFFFFFFF, float(radius), NETS[net])

@@ -19,8 +19,12 @@ reuses conv1.lin.weight / conv1.bias and ignores the attention vectors.
 ``GCN(7, 8, 9, layers=3)`` is the same class with its commented conv2/conv3 layers
 (train_gcn_dqn.py:54-55, 65-68): conv1 -> tanh -> conv2 -> relu -> conv3 -> relu ->
 lin1 -> relu -> lin2, hidden 8 — the architecture of the reference's Flocking checkpoints
-(``data/models/experiment_Flocking-seed_*.pth``), forward only (``SWARM_NET_GAT3``).
-``GCN.from_state_dict(sd)`` picks the architecture from the checkpoint's keys.
+(``data/models/experiment_Flocking-seed_*.pth``, ``SWARM_NET_GAT3``).  ``GAT3`` is that network as
+a class of its own, and the one that takes ``autograd=True``: ``loss.backward()`` then runs one
+``swarm_gat3_q_backward`` call, with the semantics above (Q bitwise the inference forward's, no
+gradient for ``data.x``).  ``DQNTrainer``, the engine and the fused tick do not train it.
+``GCN.from_state_dict(sd)`` picks the architecture from the checkpoint's keys (a ``GAT3`` for a
+checkpoint that holds conv2).
 """
 from __future__ import annotations
 
@@ -51,23 +55,24 @@ class GATConvParams(nn.Module):
 
 class _QFunction(torch.autograd.Function):
     """Q = GCN.forward(x) as one ``swarm_q_forward`` launch; backward = one ``swarm_q_backward``
-    call, its flat gradient sliced in ``param_order("gcn")``.  No gradient for x."""
+    (three-layer network: ``swarm_gat3_q_backward``) call, its flat gradient sliced in
+    ``param_order(model.net)``.  No gradient for x."""
 
     @staticmethod
     def forward(ctx, model, x, cfg, mult, *params):
         ctx.flat = model.flat_params(x.device)   # the weights this Q was computed with
-        ctx.x, ctx.cfg, ctx.mult = x, cfg, mult
+        ctx.x, ctx.cfg, ctx.mult, ctx.net = x, cfg, mult, model.net
         ctx.params = params
         return model._q_forward(ctx.flat, x, cfg, mult)
 
     @staticmethod
     def backward(ctx, dq):
         if ctx.cfg.n_envs == 0:   # an empty batch: zero gradients, nothing to launch
-            flat = torch.zeros(_lib.N_PARAMS, dtype=torch.float32, device=ctx.x.device)
+            flat = torch.zeros(sum(p.numel() for p in ctx.params), dtype=torch.float32, device=ctx.x.device)
         else:
             flat = q_backward(ctx.flat, ctx.x, ctx.cfg, ctx.mult, dq)
         grads, o = [], 0
-        for i, ((_, shape), p) in enumerate(zip(param_order("gcn"), ctx.params)):
+        for i, ((_, shape), p) in enumerate(zip(param_order(ctx.net), ctx.params)):
             n = p.numel()
             grads.append(flat[o:o + n].reshape(shape).to(p.device, p.dtype) if ctx.needs_input_grad[4 + i] else None)
             o += n
@@ -75,6 +80,8 @@ class _QFunction(torch.autograd.Function):
 
 
 class GCN(nn.Module):
+    _trains_three_layers = False   # GAT3 does
+
     def __init__(self, input_dim: int = 7, hidden_dim: int = 32, output_dim: int = 9, conv: str = "gat",
                  layers: int = 1, autograd: bool = False):
         super().__init__()
@@ -84,9 +91,9 @@ class GCN(nn.Module):
                              "Flocking checkpoints' GCN(7, 8, 9, layers=3)")
         if layers == 3 and conv != "gat":
             raise ValueError("the three-layer network is a GAT")
-        if layers == 3 and autograd:
-            raise ValueError("the three-layer network is forward only (no backward kernel): autograd=True needs "
-                             "GCN(7, 32, 9)")
+        if layers == 3 and autograd and not self._trains_three_layers:
+            raise ValueError("GCN(7, 8, 9, layers=3) is forward only: the differentiable three-layer network is "
+                             "GAT3(autograd=True); GCN(autograd=True) needs GCN(7, 32, 9)")
         self.conv1 = GATConvParams(input_dim, hidden_dim)
         if layers == 3:
             self.conv2 = GATConvParams(hidden_dim, hidden_dim)
@@ -103,9 +110,9 @@ class GCN(nn.Module):
 
     @classmethod
     def from_state_dict(cls, sd, conv: str = "gat", autograd: bool = False) -> "GCN":
-        """A model of the checkpoint's architecture (three GATConvs if it holds conv2), loaded."""
-        m = (cls(7, 8, 9, conv, layers=3, autograd=autograd) if "conv2.lin.weight" in sd
-             else cls(7, 32, 9, conv, autograd=autograd))
+        """A model of the checkpoint's architecture, loaded: a ``GAT3`` (three GATConvs) if it holds
+        conv2, else ``cls(7, 32, 9)``."""
+        m = GAT3(conv, autograd=autograd) if "conv2.lin.weight" in sd else cls(7, 32, 9, conv, autograd=autograd)
         m.load_state_dict(sd)
         return m
 
@@ -148,4 +155,13 @@ class GCN(nn.Module):
         return self._q_forward(self.flat_params(x.device), x, cfg, mult)
 
 
-__all__ = ["GCN", "GATConvParams", "_round4"]
+class GAT3(GCN):
+    """``GCN(7, 8, 9, layers=3)``, the Flocking checkpoints' network, with ``autograd`` allowed:
+    ``GAT3(autograd=True)`` is differentiable in its parameters through ``swarm_gat3_q_backward``."""
+    _trains_three_layers = True
+
+    def __init__(self, conv: str = "gat", autograd: bool = False):
+        super().__init__(7, 8, 9, conv, layers=3, autograd=autograd)
+
+
+__all__ = ["GCN", "GAT3", "GATConvParams", "_round4"]

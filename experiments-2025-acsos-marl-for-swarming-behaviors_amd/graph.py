@@ -148,16 +148,30 @@ def edges_to_mult(edge_index: torch.Tensor, n_graphs: int, n_nodes: int) -> torc
 
 def q_backward(params: torch.Tensor, x: torch.Tensor, cfg: "_lib.SwarmConfig", mult: Optional[torch.Tensor],
                dq: torch.Tensor) -> torch.Tensor:
-    """Gradient of ``(Q * dq).sum()`` with respect to the flat parameter vector (``swarm_q_backward``):
-    params [N_PARAMS], x [G*N, 7], dq [G*N, 9] on the GPU, ``cfg`` as passed to ``swarm_q_forward``
-    (``mult``: the dense multiplicities, or None).  Returns [N_PARAMS] float32 on the GPU."""
+    """Gradient of ``(Q * dq).sum()`` with respect to the flat parameter vector: ``swarm_q_backward``
+    for the one-layer network, ``swarm_gat3_q_backward`` for ``cfg.net == NET_GAT3``.
+    params [N_PARAMS] (GAT3: [409]), x [G*N, 7], dq [G*N, 9] on the GPU, ``cfg`` as passed to
+    ``swarm_q_forward`` (``mult``: the dense multiplicities, or None).  Returns the flat gradient,
+    [N_PARAMS] (GAT3: [409]) float32 on the GPU."""
     lib = _lib.load()
     dq = dq.to(x.device, torch.float32).contiguous()
     n_ws = _lib.size(lib, "swarm_td_workspace_floats", cfg, cfg.n_envs)
     ws = torch.empty(n_ws, dtype=torch.float32, device=x.device)
+    if cfg.net == _lib.NET_GAT3:
+        grad = torch.empty(_lib.GAT3_GRAD_FLOATS, dtype=torch.float32, device=x.device)
+        call(lib, "swarm_gat3_q_backward", cfg, ptr(params), ptr(x), ptr(mult), ptr(dq), ptr(ws), ptr(grad))
+        return grad[: _lib.GAT3_N_PARAMS]
     grad = torch.empty(_lib.GRAD_FLOATS, dtype=torch.float32, device=x.device)
     call(lib, "swarm_q_backward", cfg, ptr(params), ptr(x), ptr(mult), ptr(dq), ptr(ws), ptr(grad))
     return grad[: _lib.N_PARAMS]
+
+
+def gat3_backward_slab_floats(n_agents: int, n_graphs: int) -> int:
+    """Floats of workspace ``swarm_gat3_q_backward``'s first launch writes (csrc/swarm_gat3_bwd.h): one
+    416-float slab per block of 4 graphs (2 with more than 16 agents).  ``swarm_td_workspace_floats``
+    of the same shape is never less (a static_assert in swarm_gat3_bwd.hip)."""
+    waves = 4 if n_agents <= 16 else 2
+    return -(-n_graphs // waves) * _lib.GAT3_GRAD_FLOATS
 
 
 def edge_index_from_mult(mult: torch.Tensor) -> torch.Tensor:

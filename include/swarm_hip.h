@@ -37,9 +37,10 @@ enum swarm_graph { SWARM_GRAPH_COMPLETE = 0, SWARM_GRAPH_KNN = 1, SWARM_GRAPH_DE
 enum swarm_conv { SWARM_CONV_GAT = 0, SWARM_CONV_GCN = 1 };
 /* Q-network: GCN = the reference's GCN class (one GATConv, hidden 32; params N_PARAMS = 1673;
    trainable).  GAT3 = the same class with its commented conv2/conv3 layers (train_gcn_dqn.py:54-55,
-   65-68), hidden 8, 409 params: what data/models/experiment_Flocking-seed_*.pth hold.  GAT3 is
-   forward only (swarm_q_forward, swarm_act_step, swarm_rollout); the learner entry points return
-   SWARM_E_UNSUPPORTED for it. */
+   65-68), hidden 8, 409 params: what data/models/experiment_Flocking-seed_*.pth hold.  GAT3 runs
+   forward (swarm_q_forward, swarm_act_step, swarm_rollout) and has the backward for a caller's
+   dL/dQ (swarm_gat3_q_backward); the learner entry points (TD kernel, fused tick, populations)
+   and swarm_q_backward return SWARM_E_UNSUPPORTED for it. */
 enum swarm_net { SWARM_NET_GCN = 0, SWARM_NET_GAT3 = 1 };
 #define SWARM_GAT3_N_PARAMS 409
 
@@ -238,9 +239,25 @@ int swarm_q_forward(const swarm_config* cfg, const float* params, const float* x
  * SWARM_GRAD_SQ_BASE are written as by swarm_grad_reduce.
  * workspace: swarm_td_workspace_floats(cfg, cfg->n_envs) floats, need not be zeroed.
  * Two launches, no allocation, no host sync: capturable.
- * Bitwise reproducible run to run.  n_envs >= 1; SWARM_NET_GCN only (else SWARM_E_UNSUPPORTED). */
+ * Bitwise reproducible run to run.  n_envs >= 1; SWARM_NET_GCN only (else SWARM_E_UNSUPPORTED:
+ * the three-layer network's backward is swarm_gat3_q_backward). */
 int swarm_q_backward(const swarm_config* cfg, const float* params, const float* x, const uint8_t* mult,
                      const float* dq, float* workspace, float* grad, void* stream);
+
+/* The same for SWARM_NET_GAT3 (the Flocking checkpoints' three GATConvs, hidden 8): params [409],
+ * x [B*N][7], mult as swarm_q_forward, dq [B*N][9].
+ * grad holds SWARM_GAT3_GRAD_FLOATS floats: grad[i] = sum over nodes n and actions a of
+ * dq[n][a] * dQ[n][a]/dtheta_i for i < 409 in the checkpoint's flat order, grad[409..415] = 0.
+ * No norm partials (the caller clips).
+ * workspace: swarm_td_workspace_floats(cfg, cfg->n_envs) floats, need not be zeroed.
+ * Two launches, no allocation, no host sync: capturable.  Bitwise reproducible run to run.
+ * Checks, in this order: the configuration as for swarm_q_forward but n_envs >= 1
+ * (SWARM_E_BADARG / SWARM_E_KNN_K; GAT3 with GCNConv: SWARM_E_BADARG); net != SWARM_NET_GAT3:
+ * SWARM_E_UNSUPPORTED (swarm_q_backward is that network's); a NULL params / x / dq / workspace /
+ * grad: SWARM_E_BADARG; SWARM_GRAPH_DENSE with a NULL mult: SWARM_E_BADARG. */
+#define SWARM_GAT3_GRAD_FLOATS 416   /* 409 gradients, then zeros */
+int swarm_gat3_q_backward(const swarm_config* cfg, const float* params, const float* x, const uint8_t* mult,
+                          const float* dq, float* workspace, float* grad, void* stream);
 
 /* Fused acting tick (train_gcn_dqn.py:161-172 / simulator.py:59-68):
  * graph -> GAT Q -> eps-greedy (ctrl->eps, Philox) -> env.step -> replay push

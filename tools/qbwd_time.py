@@ -8,7 +8,12 @@ captured tick):
 at S = B graphs of N agents, complete graph, GAT.  The chains alternate, `--repeats` times each, after
 a warm-up of both; the table gives the median and the spread of the per-call time of each chain.
 
-usage: python tools/qbwd_time.py [--calls 2000] [--repeats 7] [--out qbwd_time.json]
+`--net gat3` times the three-layer network's pair instead, at Flocking 8 x 1024 graphs, complete graph:
+  gat3_q_backward : swarm_gat3_q_backward             (backward kernel + its slab reduce)
+  gat3_q_forward  : swarm_q_forward with SWARM_NET_GAT3  (one launch; the forward of the same graphs)
+on the Flocking fixture's weights of seed 4.  A record, not a gate: nothing comparable existed before.
+
+usage: python tools/qbwd_time.py [--net gcn|gat3] [--calls 2000] [--repeats 7] [--out qbwd_time.json]
 Prints one JSON line per configuration.
 """
 import argparse
@@ -25,6 +30,8 @@ import swarm_amd  # noqa: E402
 import swarm_amd._lib as L  # noqa: E402
 
 CONFIGS = (("GoTo", 8, 1024), ("ObstacleAvoidance", 12, 1024))
+GAT3_CONFIGS = (("Flocking", 8, 1024),)
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def chain_us(fn, calls):
@@ -35,6 +42,52 @@ def chain_us(fn, calls):
     b.record()
     b.synchronize()
     return a.elapsed_time(b) * 1e3 / calls
+
+
+def alternate(chains, calls, repeats, out):
+    """Warm both chains up, alternate them `repeats` times; medians and spreads into `out`."""
+    for fn in chains.values():   # warm-up: code objects loaded, clocks up
+        chain_us(fn, max(calls // 4, 10))
+    times = {k: [] for k in chains}
+    for _ in range(repeats):
+        for k, fn in chains.items():
+            times[k].append(chain_us(fn, calls))
+    for k, v in times.items():
+        out[k + "_us"] = round(statistics.median(v), 3)
+        out[k + "_us_min_max"] = [round(min(v), 3), round(max(v), 3)]
+    return out
+
+
+def measure_gat3(scen, N, S, calls, repeats):
+    import numpy as np
+    lib = L.load()
+    w = np.load(os.path.join(ROOT, "tests", "golden", "flocking_weights.npz"))["weights_flocking"][4]
+    params = torch.tensor(w).cuda()
+    g = torch.Generator().manual_seed(N)
+    s = (torch.randn(S, N, 4, generator=g) * 0.4).cuda()
+    ids = torch.arange(N, dtype=torch.float32, device="cuda").view(1, N, 1).expand(S, N, 1)
+    goal = torch.tensor([-0.8, 0.8], device="cuda").expand(S, N, 2)
+    x = torch.cat([s, goal, ids], dim=-1).reshape(S * N, 7).contiguous()
+    dq = torch.randn(S * N, 9, generator=g).cuda()
+    cfg = L.SwarmConfig(S, N, L.SWARM_FLOCKING, L.GRAPH_COMPLETE, 0, L.CONV_GAT, 0, 0, 0, 0.0, L.NET_GAT3)
+    ws = torch.empty(lib.swarm_td_workspace_floats(ctypes.byref(cfg), S), dtype=torch.float32, device="cuda")
+    grad = torch.empty(L.GAT3_GRAD_FLOATS, dtype=torch.float32, device="cuda")
+    q = torch.empty(S * N, 9, dtype=torch.float32, device="cuda")
+    st = L.stream_ptr()
+    bargs = (ctypes.byref(cfg), L.ptr(params), L.ptr(x), None, L.ptr(dq), L.ptr(ws), L.ptr(grad), st)
+    fargs = (ctypes.byref(cfg), L.ptr(params), L.ptr(x), None, L.ptr(q), st)
+
+    def qb():
+        L.check(lib.swarm_gat3_q_backward(*bargs), "swarm_gat3_q_backward")
+
+    def qf():
+        L.check(lib.swarm_q_forward(*fargs), "swarm_q_forward")
+
+    out = {"net": "gat3", "scenario": scen, "n_agents": N, "graphs": S, "calls_per_chain": calls, "repeats": repeats,
+           "build": lib.swarm_build_info().decode()}
+    alternate({"gat3_q_backward": qb, "gat3_q_forward": qf}, calls, repeats, out)
+    out["ratio"] = round(out["gat3_q_backward_us"] / out["gat3_q_forward_us"], 3)
+    return out
 
 
 def measure(scen, N, S, calls, repeats):
@@ -63,18 +116,9 @@ def measure(scen, N, S, calls, repeats):
     def qb():
         L.check(lib.swarm_q_backward(*args), "swarm_q_backward")
 
-    chains = {"q_backward": qb, "td_pair": eng.td_grad}
-    for fn in chains.values():   # warm-up: code objects loaded, clocks up
-        chain_us(fn, max(calls // 4, 10))
-    times = {k: [] for k in chains}
-    for _ in range(repeats):
-        for k, fn in chains.items():
-            times[k].append(chain_us(fn, calls))
     out = {"scenario": scen, "n_agents": N, "graphs": S, "calls_per_chain": calls, "repeats": repeats,
            "build": lib.swarm_build_info().decode()}
-    for k, v in times.items():
-        out[k + "_us"] = round(statistics.median(v), 3)
-        out[k + "_us_min_max"] = [round(min(v), 3), round(max(v), 3)]
+    alternate({"q_backward": qb, "td_pair": eng.td_grad}, calls, repeats, out)
     out["ratio"] = round(out["q_backward_us"] / out["td_pair_us"], 3)
     return out
 
@@ -84,8 +128,12 @@ def main():
     ap.add_argument("--calls", type=int, default=2000)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--net", choices=("gcn", "gat3"), default="gcn")
     a = ap.parse_args()
-    rows = [measure(scen, N, S, a.calls, a.repeats) for scen, N, S in CONFIGS]
+    if a.net == "gat3":
+        rows = [measure_gat3(scen, N, S, a.calls, a.repeats) for scen, N, S in GAT3_CONFIGS]
+    else:
+        rows = [measure(scen, N, S, a.calls, a.repeats) for scen, N, S in CONFIGS]
     for r in rows:
         print(json.dumps(r))
     if a.out:
