@@ -4,9 +4,11 @@ the reference's scripts import from it, backed by the MI355X path.
     GCN                  train_gcn_dqn.py:50-70   (same state_dict keys; data/models/*.pth load)
     GAT3                 the same class with its commented conv2 / conv3 layers (:54-55, :65-68), hidden 8:
                          the Flocking checkpoints' network, differentiable with autograd=True
+    SwarmGat3Engine      the device learner of GAT3 (DQNTrainer(..., net="gat3") drives it)
     GraphReplayBuffer    :25-48
     DQNTrainer           :72-231  (create_graph_from_observations, train_step_dqn, train_model,
-                                   save_metrics_to_csv; the episode loop runs fused on the GPU)
+                                   save_metrics_to_csv; the episode loop runs fused on the GPU;
+                                   net="gat3" trains the Flocking checkpoints' network)
     set_seed             :233-239
     get_scenario         :241-249
 
@@ -21,9 +23,10 @@ _ROOT = _os.path.dirname(_os.path.dirname(_os.path.dirname(_os.path.dirname(_os.
 if _ROOT not in _sys.path:
     _sys.path.append(_ROOT)
 
-from swarm_amd import GAT3, GCN, DQNTrainer, GraphReplayBuffer, get_scenario, make_env, set_seed  # noqa: E402,F401
+from swarm_amd import (GAT3, GCN, DQNTrainer, GraphReplayBuffer, SwarmGat3Engine, get_scenario, make_env,  # noqa: E402,F401
+                       set_seed)
 
-__all__ = ["GCN", "GAT3", "DQNTrainer", "GraphReplayBuffer", "set_seed", "get_scenario", "main"]
+__all__ = ["GCN", "GAT3", "SwarmGat3Engine", "DQNTrainer", "GraphReplayBuffer", "set_seed", "get_scenario", "main"]
 
 
 def main(max_seed=10, experiments=("ObstacleAvoidance", "GoTo"), agents=10, episodes=1000,

@@ -22,7 +22,7 @@ F_SHARED_RESET, F_RANDOM_OA = 1, 2
 N_PARAMS = 1673
 NET_GCN, NET_GAT3 = 0, 1
 GAT3_N_PARAMS = 409
-GAT3_GRAD_FLOATS = 416    # SWARM_GAT3_GRAD_FLOATS: 409 gradients, then zeros
+GAT3_GRAD_FLOATS = 416    # SWARM_GAT3_GRAD_FLOATS: 409 gradients, [409] the TD path's loss sum, zeros
 GRAD_FLOATS = 1792        # SWARM_GRAD_FLOATS: gradient, loss sum, the clip norm's group partials
 GRAD_SQ_BASE = 1680       # SWARM_GRAD_SQ_BASE
 ADAM_F_NORM_PARTIALS = 1  # swarm_adam_cfg.flags
@@ -125,6 +125,12 @@ _PROTOS = {
                                    c_stream]),
     "swarm_gat3_q_backward": (c_int32, [POINTER(SwarmConfig), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_stream]),
+    # (cfg, hp, params, target, replay, ctrl, sample_in, sample_out, workspace, grad, stream)
+    "swarm_gat3_td_grad": (c_int32, [POINTER(SwarmConfig), POINTER(SwarmAdamCfg), c_void_p, c_void_p,
+                                     POINTER(SwarmReplay), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_stream]),
+    # (cfg, hp, params, target, adam_m, adam_v, grad, replay_capacity, ctrl, stream)
+    "swarm_gat3_adam_step": (c_int32, [POINTER(SwarmConfig), POINTER(SwarmAdamCfg), c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_int32, c_void_p, c_stream]),
     "swarm_act_step": (c_int32, [POINTER(SwarmConfig), c_void_p, c_void_p, POINTER(SwarmReplay), c_void_p,
                                  POINTER(SwarmActOut), c_stream]),
     "swarm_train_act_step": (c_int32, [POINTER(SwarmConfig), POINTER(SwarmAdamCfg), POINTER(SwarmLearner), c_void_p,
@@ -179,7 +185,7 @@ EXPORTED = tuple(_PROTOS)
 # added under ABI 10 after other additions: a library of an earlier build of the same ABI (the A / B
 # side of tools/bitcmp.py, SWARM_LIB_PATH) lacks it and still loads; calling it there raises.  The
 # in-tree library must have every symbol (__graft_entry__.build, tests/test_cpu_host.py).
-_NEWEST = ("swarm_gat3_q_backward",)
+_NEWEST = ("swarm_gat3_q_backward", "swarm_gat3_td_grad", "swarm_gat3_adam_step")
 
 _lib = None
 

@@ -104,22 +104,51 @@ __device__ __forceinline__ void g3b_outer(float* out, int count, int KB, const f
   }
 }
 
+// ---- the wave's work in phases (g3b_wave runs them in this order; the TD kernel of swarm_gat3_td.h
+// runs the graph and forward phases twice, on rows it loads from the replay, before one backward)
+// the graph of the wave: its kind is read at run time; mult is SWARM_GRAPH_DENSE's, of graph gid
+struct G3bGraph {
+  int N, graph, k;
+  float radius;
+  const uint8_t* mult;
+  int gid;
+};
+// the lane's registers between the phases: its slots, its nodes' in-edge multiplicities (one graph
+// for all layers, forward and backward), and what the keeping forward keeps outside LDS
 template <int NS>
-__device__ __forceinline__ void g3b_wave(const float* __restrict__ P, G3bWave<NS>& W, float* __restrict__ part,
-                                         const int gid, const G3bArgs& A) {
-  constexpr int CT = DGeom<NS>::CT;
-  const int lane = threadIdx.x & 63, c = lane & 15, p = lane >> 4;
-  const bool pb0 = (p & 1) != 0, pb1 = (p & 2) != 0;
-  const int N = A.N, graph = A.graph;
-  WSmall<NS>& sm = W.sm;
+struct G3bKeep {
+  static constexpr int CT = DGeom<NS>::CT;
+  static constexpr bool kKeepM = NS <= 16;
   bool st[CT];   // the lane's slot exists (n < NS): it stores
   int nn[CT];    // the slot it reads
-  float dqv[CT][kActions];
+  int mk[kKeepM ? CT : 1][kKeepM ? NS : 1];
+  float sdst[3][CT], emx[3][CT], inv[3][CT], outv[3][CT][2];
+  float zv[CT][2];   // relu(lin1), the lane's features
+};
+
+template <int NS>
+__device__ __forceinline__ void g3b_slots(G3bKeep<NS>& K) {
+  const int c = threadIdx.x & 15;
+#pragma unroll
+  for (int ct = 0; ct < G3bKeep<NS>::CT; ++ct) {
+    const int n = 16 * ct + c;
+    K.st[ct] = n < NS;
+    K.nn[ct] = min(n, NS - 1);
+  }
+}
+
+// loading phase of swarm_gat3_q_backward: x and dq rows of graph gid from the caller's arrays into
+// X[0], px / py and DQ; dqv = the lane's nodes' dq rows
+template <int NS>
+__device__ __forceinline__ void g3b_load(G3bWave<NS>& W, const G3bKeep<NS>& K, const int gid, const G3bArgs& A,
+                                         float (&dqv)[DGeom<NS>::CT][kActions]) {
+  constexpr int CT = DGeom<NS>::CT;
+  const int lane = threadIdx.x & 63, c = lane & 15, p = lane >> 4;
+  const int N = A.N;
+  WSmall<NS>& sm = W.sm;
 #pragma unroll
   for (int ct = 0; ct < CT; ++ct) {
     const int n = 16 * ct + c;
-    st[ct] = n < NS;
-    nn[ct] = min(n, NS - 1);
     const bool nv = n < N;
     // slots that are no node alias an in-bounds one and are zeroed after the load
     const size_t node = (size_t)gid * N + min(n, N - 1);
@@ -130,7 +159,7 @@ __device__ __forceinline__ void g3b_wave(const float* __restrict__ P, G3bWave<NS
       const float g = A.dq[node * kActions + a];
       dqv[ct][a] = nv ? g : 0.0f;
     }
-    if (st[ct]) {
+    if (K.st[ct]) {
       W.X[0][n][p] = xa;
       W.X[0][n][4 + p] = xb;
       if (p == 0) sm.px[n] = xa;
@@ -141,17 +170,27 @@ __device__ __forceinline__ void g3b_wave(const float* __restrict__ P, G3bWave<NS
       }
     }
   }
+}
+
+// graph phase, after a loading phase's X[0] / px / py stores: the neighbour masks and the lane's
+// in-edge multiplicities
+template <int NS>
+__device__ __forceinline__ void g3b_graph(G3bWave<NS>& W, const G3bGraph& G, G3bKeep<NS>& K) {
+  constexpr int CT = DGeom<NS>::CT;
+  const int lane = threadIdx.x & 63, c = lane & 15, p = lane >> 4;
+  const int N = G.N, graph = G.graph;
+  WSmall<NS>& sm = W.sm;
   wave_lds_sync();
   // ---- neighbour masks: gat3_forward's graph phase, its scratch in ks (no backward row is live yet)
   if (graph == SWARM_GRAPH_KNN) {
     if constexpr (NS <= 16) {
-      knn_masks_wave<NS, NS>(lane, N, A.k, sm, W.ks, reinterpret_cast<KV*>(W.ks + NS * NS));
+      knn_masks_wave<NS, NS>(lane, N, G.k, sm, W.ks, reinterpret_cast<KV*>(W.ks + NS * NS));
     } else {
 #pragma unroll
       for (int ct = 0; ct < CT; ++ct) {
         const int n = 16 * ct + c;
-        KV* q = reinterpret_cast<KV*>(W.ks + NS * NS) + nn[ct] * NS;
-        if (n < NS && p == 0) sm.knn[n] = (n < N) ? knn_mask_node<NS, NS>(n, N, A.k, sm, q) : 0u;
+        KV* q = reinterpret_cast<KV*>(W.ks + NS * NS) + K.nn[ct] * NS;
+        if (n < NS && p == 0) sm.knn[n] = (n < N) ? knn_mask_node<NS, NS>(n, N, G.k, sm, q) : 0u;
       }
     }
     wave_lds_sync();
@@ -159,28 +198,39 @@ __device__ __forceinline__ void g3b_wave(const float* __restrict__ P, G3bWave<NS
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) {
       const int n = 16 * ct + c;
-      if (n < NS && p == 0) sm.knn[n] = radius_mask_node<NS, NS>(n, N, A.radius, sm);
+      if (n < NS && p == 0) sm.knn[n] = radius_mask_node<NS, NS>(n, N, G.radius, sm);
     }
     wave_lds_sync();
   }
-  // in-edge multiplicities of the lane's node: one graph for all layers, forward and backward
-  constexpr bool kKeepM = NS <= 16;
-  int mk[kKeepM ? CT : 1][kKeepM ? NS : 1];
-  if constexpr (kKeepM) {
+  if constexpr (G3bKeep<NS>::kKeepM) {
 #pragma unroll
-    for (int ct = 0; ct < CT; ++ct) in_mults<NS>(nn[ct], N, graph, sm, A.mult, gid, mk[ct]);
+    for (int ct = 0; ct < CT; ++ct) in_mults<NS>(K.nn[ct], N, graph, sm, G.mult, G.gid, K.mk[ct]);
   }
-  auto mults = [&](int ct, int (&m)[NS]) {
-    if constexpr (kKeepM) {
+}
+// in-edge multiplicities of the lane's node of column tile ct
+template <int NS>
+__device__ __forceinline__ void g3b_mults(const G3bWave<NS>& W, const G3bGraph& G, const G3bKeep<NS>& K, int ct,
+                                          int (&m)[NS]) {
+  if constexpr (G3bKeep<NS>::kKeepM) {
 #pragma unroll
-      for (int u = 0; u < NS; ++u) m[u] = mk[ct][u];
-    } else {
-      in_mults<NS>(nn[ct], N, graph, sm, A.mult, gid, m);
-    }
-  };
+    for (int u = 0; u < NS; ++u) m[u] = K.mk[ct][u];
+  } else {
+    in_mults<NS>(K.nn[ct], G.N, G.graph, W.sm, G.mult, G.gid, m);
+  }
+}
 
-  // ---- the keeping forward
-  float sdst[3][CT], emx[3][CT], inv[3][CT], outv[3][CT][2];
+// the keeping forward on X[0] with the weights P: conv1..3 and lin1 + relu (Z rows stored, not synced)
+template <int NS>
+__device__ __forceinline__ void g3b_forward(const float* __restrict__ P, G3bWave<NS>& W, const G3bGraph& G,
+                                            G3bKeep<NS>& Kp) {
+  constexpr int CT = DGeom<NS>::CT;
+  const int c = threadIdx.x & 15, p = (threadIdx.x & 63) >> 4;
+  const bool (&st)[CT] = Kp.st;
+  const int (&nn)[CT] = Kp.nn;
+  float (&sdst)[3][CT] = Kp.sdst, (&emx)[3][CT] = Kp.emx, (&inv)[3][CT] = Kp.inv, (&outv)[3][CT][2] = Kp.outv;
+  float (&zv)[CT][2] = Kp.zv;
+  auto mults = [&](int ct, int (&m)[NS]) { g3b_mults<NS>(W, G, Kp, ct, m); };
+
 #pragma unroll
   for (int l = 0; l < 3; ++l) {
     const float* Pc = P + g3_conv_off(l);
@@ -250,7 +300,6 @@ __device__ __forceinline__ void g3b_wave(const float* __restrict__ P, G3bWave<NS
     wave_lds_sync();
   }
   // lin1 + relu
-  float zv[CT][2];
 #pragma unroll
   for (int ct = 0; ct < CT; ++ct) {
     float x[kH3];
@@ -266,6 +315,22 @@ __device__ __forceinline__ void g3b_wave(const float* __restrict__ P, G3bWave<NS
     }
     if (st[ct]) *reinterpret_cast<float2*>(&W.Z[16 * ct + c][2 * p]) = make_float2(zv[ct][0], zv[ct][1]);
   }
+}
+
+// the backward for the lane's dq rows dqv (their copies in DQ): the head and conv3, conv2, conv1;
+// the wave's 409 partials into part
+template <int NS>
+__device__ __forceinline__ void g3b_backward(const float* __restrict__ P, G3bWave<NS>& W, float* __restrict__ part,
+                                             const G3bGraph& G, const G3bKeep<NS>& Kp,
+                                             const float (&dqv)[DGeom<NS>::CT][kActions]) {
+  constexpr int CT = DGeom<NS>::CT;
+  const int lane = threadIdx.x & 63, c = lane & 15, p = lane >> 4;
+  const bool pb0 = (p & 1) != 0, pb1 = (p & 2) != 0;
+  const bool (&st)[CT] = Kp.st;
+  const int (&nn)[CT] = Kp.nn;
+  const float (&sdst)[3][CT] = Kp.sdst, (&emx)[3][CT] = Kp.emx, (&inv)[3][CT] = Kp.inv, (&outv)[3][CT][2] = Kp.outv;
+  const float (&zv)[CT][2] = Kp.zv;
+  auto mults = [&](int ct, int (&m)[NS]) { g3b_mults<NS>(W, G, Kp, ct, m); };
 
   // ---- head: dZ = (W2^T dq) [z > 0], dO3 = W1^T dZ
   float dO[CT][2];   // d(loss) / d(activated output) of the layer below, the lane's features
@@ -416,6 +481,19 @@ __device__ __forceinline__ void g3b_wave(const float* __restrict__ P, G3bWave<NS
 }
 
 template <int NS>
+__device__ __forceinline__ void g3b_wave(const float* __restrict__ P, G3bWave<NS>& W, float* __restrict__ part,
+                                         const int gid, const G3bArgs& A) {
+  const G3bGraph G = {A.N, A.graph, A.k, A.radius, A.mult, gid};
+  G3bKeep<NS> K;
+  float dqv[DGeom<NS>::CT][kActions];
+  g3b_slots<NS>(K);
+  g3b_load<NS>(W, K, gid, A, dqv);
+  g3b_graph<NS>(W, G, K);
+  g3b_forward<NS>(P, W, G, K);
+  g3b_backward<NS>(P, W, part, G, K, dqv);
+}
+
+template <int NS>
 __global__ __launch_bounds__(64 * g3b_waves(NS)) void gat3_backward_kernel(G3bArgs A) {
   constexpr int WPB = g3b_waves(NS), NT = 64 * WPB;
   __shared__ G3bSmem<NS> L;
@@ -447,6 +525,9 @@ __global__ __launch_bounds__(64 * g3b_waves(NS)) void gat3_backward_kernel(G3bAr
 constexpr int kG3RedCols = 16, kG3RedGroups = 64;
 constexpr int kG3RedBlocks = kG3Cols / kG3RedCols;
 
+// LOSS = 1 (the TD path, swarm_gat3_td.h): column 409, the batch's sum of squared TD errors, is
+// carried through as well; 0: grad[409..415] = 0
+template <int LOSS>
 __global__ __launch_bounds__(kG3RedCols * kG3RedGroups) void gat3_grad_reduce_kernel(const float* __restrict__ slabs,
                                                                                     int n_slabs,
                                                                                     float* __restrict__ grad) {
@@ -471,7 +552,7 @@ __global__ __launch_bounds__(kG3RedCols * kG3RedGroups) void gat3_grad_reduce_ke
     float tot = part2[0][c];
 #pragma unroll
     for (int gi = 1; gi < kG3RedGroups / 8; ++gi) tot = tot + part2[gi][c];
-    grad[col] = col < G3_N_PARAMS ? tot : 0.0f;
+    grad[col] = col < G3_N_PARAMS + LOSS ? tot : 0.0f;
   }
 }
 

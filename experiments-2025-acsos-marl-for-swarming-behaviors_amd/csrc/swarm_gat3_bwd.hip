@@ -23,7 +23,7 @@ int gat3_bwd_launch(const G3bArgs& A, hipStream_t stream) {
     hipLaunchKernelGGL((gat3_backward_kernel<NS>), dim3(A.n_slabs), dim3(64 * g3b_waves(NS)), 0, stream, A);
   });
   if (int e = (int)hipGetLastError()) return e;
-  hipLaunchKernelGGL(gat3_grad_reduce_kernel, dim3(kG3RedBlocks), dim3(kG3RedCols * kG3RedGroups), 0, stream,
+  hipLaunchKernelGGL(gat3_grad_reduce_kernel<0>, dim3(kG3RedBlocks), dim3(kG3RedCols * kG3RedGroups), 0, stream,
                      (const float*)A.slabs, A.n_slabs, A.grad);
   return (int)hipGetLastError();
 }

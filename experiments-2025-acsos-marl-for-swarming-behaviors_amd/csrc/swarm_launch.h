@@ -15,7 +15,7 @@ struct CfgRules {
   bool dense_ok;      // SWARM_GRAPH_DENSE (a caller-supplied multiplicity) is accepted
   bool empty_ok;      // n_envs == 0 is a valid no-op
   bool env_checked;   // scenario and conv are validated (the TD side has always taken them as given)
-  bool learner;       // any net but the GCN is SWARM_E_UNSUPPORTED (GAT3 has swarm_gat3_q_backward only)
+  bool learner;       // any net but the GCN is SWARM_E_UNSUPPORTED (GAT3 has entry points of its own: swarm_gat3_*)
   bool hp_checked;    // hp is required: batch first, world_size / update_target_every last of all
 };
 constexpr CfgRules kCfgAct = {32, true, true, true, false, false};        // acting / env entry points
@@ -24,6 +24,9 @@ constexpr CfgRules kCfgTd = {32, false, false, false, true, true};        // TD,
 constexpr CfgRules kCfgTick = {16, false, false, true, true, false};      // swarm_train_tick
 constexpr CfgRules kCfgQBackward = {32, true, false, true, true, false};  // swarm_q_backward: kCfgAct for a learner
 constexpr CfgRules kCfgGat3Backward = {32, true, false, true, false, false};   // swarm_gat3_q_backward: kCfgAct, n_envs >= 1
+// swarm_gat3_td_grad / swarm_gat3_adam_step: kCfgTd with the net rule turned round (the entry points refuse the
+// GCN themselves, then world_size != 1, and only then the dense graph)
+constexpr CfgRules kCfgGat3Td = {32, true, false, false, false, true};
 // 0 or the first error, in the order the entry points have always reported them (tests/test_cpu_host.py)
 inline int check_config(const swarm_config* c, const CfgRules& r, const swarm_adam_cfg* hp = nullptr) {
   if (!c || c->n_agents < 1 || c->n_agents > r.max_agents || c->n_envs < (r.empty_ok ? 0 : 1)) return SWARM_E_BADARG;

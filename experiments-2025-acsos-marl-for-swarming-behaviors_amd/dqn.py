@@ -9,6 +9,12 @@ as ``experiment_{experiment}-seed_{seed}.pth`` (:201) and the stats CSV with the
 reference's ``i // 10`` indexing (:225-231).  One episode is captured once into a
 hipGraph and replayed.
 
+``DQNTrainer(..., net="gat3")`` trains the Flocking checkpoints' three-layer GAT (``GAT3`` models, a
+``SwarmGat3Engine``): the same loop, each tick four launches (act + push, TD gradient, optimizer step)
+instead of the fused two, captured and replayed the same way; the saved ``.pth`` has that network's
+keys.  Whether a tick ran an update is taken from ``ctrl.adam_step`` advancing (its optimizer step is
+applied at once, so ``trained`` stays 0).  Such a trainer cannot join a ``PopulationTrainer``.
+
 Optional evaluation inside training (not in the reference, whose training loop never evaluates):
 with ``config["eval_every"] = E`` every E-th episode ends with a greedy rollout of the current
 weights on ``eval_envs`` evaluation environments (``eval_seed``; ``eval_graph`` / ``eval_knn_k``
@@ -40,8 +46,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine import SwarmEngine, flatten_state_dict, glorot_init, unflatten_params
-from .gcn import GCN
+from .engine import SwarmEngine, SwarmGat3Engine, flatten_state_dict, glorot_init, unflatten_params
+from .gcn import GAT3, GCN
 from .graph import Batch, Data, create_graph_from_observations
 from .population import SwarmPopulation, evaluation_engine
 
@@ -110,7 +116,10 @@ def set_seed(seed: int):
 class DQNTrainer:
     def __init__(self, env, seed: int, models_path: str, stats_path: str, experiment: str, *,
                  batch_size: int = 32, update_target_every: int = 200, lr: float = 1e-3, gamma: float = 0.99,
-                 replay_capacity: int = 1_000_000, use_graph: bool = True):
+                 replay_capacity: int = 1_000_000, use_graph: bool = True, net: str = "gcn"):
+        if net not in ("gcn", "gat3"):
+            raise ValueError(f"net must be 'gcn' or 'gat3', not {net!r}")
+        self.net = net
         self.env = env
         self.seed = seed
         self.models_path = models_path
@@ -118,19 +127,24 @@ class DQNTrainer:
         self.experiment = experiment
         self.n_input = env.observation_space["agent0"].shape[0] + 1
         self.n_output = env.action_space["agent0"].n
-        self.model = GCN(input_dim=self.n_input, hidden_dim=32, output_dim=self.n_output)
-        init = glorot_init(torch.Generator().manual_seed(seed))
-        self.model.load_state_dict(unflatten_params(init))
-        self.target_model = GCN(input_dim=self.n_input, hidden_dim=32, output_dim=self.n_output)
+        if net == "gat3":   # the Flocking checkpoints' three-layer network, trained by SwarmGat3Engine
+            self.model, self.target_model = GAT3(), GAT3()
+            init = glorot_init(torch.Generator().manual_seed(seed), net)
+        else:
+            self.model = GCN(input_dim=self.n_input, hidden_dim=32, output_dim=self.n_output)
+            self.target_model = GCN(input_dim=self.n_input, hidden_dim=32, output_dim=self.n_output)
+            init = glorot_init(torch.Generator().manual_seed(seed))
+        self.model.load_state_dict(unflatten_params(init, net))
         self.target_model.load_state_dict(self.model.state_dict())
         self.batch_size = batch_size
         self.update_target_every = update_target_every
         self.use_graph = use_graph
         scen = env.scenario
-        self.engine = SwarmEngine(scenario=scen.SCENARIO_ID, n_agents=env.n_agents, n_envs=env.num_envs,
-                                  seed=seed, params=init, batch=batch_size, gamma=gamma, lr=lr,
-                                  update_target_every=update_target_every, replay_capacity=replay_capacity,
-                                  shared_reset=True, random_oa=bool(getattr(scen, "random", False)))
+        engine_cls = SwarmGat3Engine if net == "gat3" else SwarmEngine
+        self.engine = engine_cls(scenario=scen.SCENARIO_ID, n_agents=env.n_agents, n_envs=env.num_envs,
+                                 seed=seed, params=init, batch=batch_size, gamma=gamma, lr=lr,
+                                 update_target_every=update_target_every, replay_capacity=replay_capacity,
+                                 shared_reset=True, random_oa=bool(getattr(scen, "random", False)))
         self.optimizer = SimpleAdamView(self.engine)
         self.replay_buffer = _EngineReplayView(self.engine)
         self.writer = SummaryWriter()
@@ -148,8 +162,8 @@ class DQNTrainer:
 
     def _sync_models(self):
         self.engine.flush()
-        self.model.load_state_dict(unflatten_params(self.engine.params.detach().cpu()))
-        self.target_model.load_state_dict(unflatten_params(self.engine.target.detach().cpu()))
+        self.model.load_state_dict(unflatten_params(self.engine.params.detach().cpu(), self.net))
+        self.target_model.load_state_dict(unflatten_params(self.engine.target.detach().cpu(), self.net))
 
     def train_step_dqn(self, batch_size, model=None, target_model=None, ticks=None, gamma=0.99,
                        update_target_every=10) -> float:
@@ -180,15 +194,21 @@ class DQNTrainer:
         n = self.env.n_agents
         calls = [0]
 
+        # the unfused optimizer step (net="gat3") leaves `trained` 0: an update ran iff adam_step advanced
+        unfused = self.net == "gat3"
+        step_before = torch.zeros((), dtype=torch.int32, device=eng.device)
+
         def tick():
             i = calls[0] % max_steps
             calls[0] += 1
+            if unfused:
+                step_before.copy_(eng.ctrl[_lib.CTRL["adam_step"]])
             eng.train_tick(full_out=False)
             self._acc_reward.add_(eng.reward[:, 0].mean() / n)
             self._acc_loss.add_(eng.ctrl.view(torch.float32)[5])
             self._tick_reward[i].copy_(eng.reward.sum(dim=1).mean())
             self._tick_loss[i].copy_(eng.ctrl.view(torch.float32)[5])
-            self._tick_trained[i].copy_(eng.ctrl[7])
+            self._tick_trained[i].copy_(eng.ctrl[_lib.CTRL["adam_step"]] - step_before if unfused else eng.ctrl[7])
         return tick
 
     def _check_episode(self):
@@ -253,6 +273,9 @@ class PopulationTrainer:
     def __init__(self, trainers):
         self.trainers = list(trainers)
         first = self.trainers[0]
+        if any(t.net != "gcn" for t in self.trainers):
+            raise ValueError("a population trains the one-layer network: DQNTrainer(net='gat3') trains alone "
+                             "(SwarmGat3Engine has the unfused tick only)")
         for t in self.trainers:
             if (t.env.max_steps, t.env.n_agents, t.use_graph) != (first.env.max_steps, first.env.n_agents,
                                                                    first.use_graph):
@@ -360,7 +383,8 @@ def _train_loop(driver, group, trainers, shape, config, prefix: str, saved: str)
     pbt_every = pbt_schedule(config)
     if pbt_every is not None:
         if not hasattr(driver, "_pbt_round"):
-            raise ValueError("pbt_every needs a PopulationTrainer: a lone trainer has nobody to exploit")
+            raise ValueError("pbt_every needs a PopulationTrainer: a lone trainer has nobody to exploit (and "
+                             "DQNTrainer(net='gat3') cannot join one)")
         group.per_member_hp = True   # before the episode is captured: the rows will change
     epsilon = initial_epsilon
     driver._acc_reward = torch.zeros(shape, device=group.device)

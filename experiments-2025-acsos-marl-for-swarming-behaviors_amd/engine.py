@@ -27,6 +27,11 @@ applies the last pending step.  The unfused sequence (``act`` + ``td_update``:
 act / td_grad / grad_reduce / adam_step) is kept for API calls and as the parity
 reference of the fused one (bit-identical, tests/test_gpu_parity.py).
 
+``SwarmGat3Engine`` is the learner of the Flocking checkpoints' three-layer GAT (``net="gat3"``):
+its tick is the unfused sequence with that network's own entry points (swarm_act_step ->
+swarm_gat3_td_grad -> swarm_gat3_adam_step, four launches); ``SwarmEngine`` itself runs that network
+forward only (``learn=False``).
+
 Every launch goes to torch's current stream, so a run of ticks can be captured
 once into a hipGraph (``capture``) and replayed.  There is no CPU fallback.
 """
@@ -80,10 +85,10 @@ def unflatten_params(flat: torch.Tensor, net: str = "gcn") -> dict:
     return out
 
 
-def glorot_init(generator: torch.Generator) -> torch.Tensor:
-    """Fresh GCN parameters: glorot for GATConv weights/attention (PyG reset_parameters),
-    torch.nn.Linear default init for lin1/lin2, zero GAT bias.  Init is not pinned by
-    any reference artefact; training runs normally start from it."""
+def glorot_init(generator: torch.Generator, net: str = "gcn") -> torch.Tensor:
+    """Fresh parameters of ``net``: glorot for GATConv weights/attention (PyG reset_parameters),
+    torch.nn.Linear default init for lin1/lin2, zero GAT bias, drawn in the flat parameter order.
+    Init is not pinned by any reference artefact; training runs normally start from it."""
     def glorot(shape, fan_in, fan_out):
         a = math.sqrt(6.0 / (fan_in + fan_out))
         return (torch.rand(shape, generator=generator) * 2 - 1) * a
@@ -94,18 +99,22 @@ def glorot_init(generator: torch.Generator) -> torch.Tensor:
         bias = (torch.rand(out_f, generator=generator) * 2 - 1) * b
         return w, bias
 
-    sd = {
-        "conv1.att_src": glorot((1, 1, 32), 1, 32),
-        "conv1.att_dst": glorot((1, 1, 32), 1, 32),
-        "conv1.bias": torch.zeros(32),
-        "conv1.lin.weight": glorot((32, 7), 7, 32),
-    }
-    sd["lin1.weight"], sd["lin1.bias"] = linear(32, 32)
-    sd["lin2.weight"], sd["lin2.bias"] = linear(9, 32)
-    return flatten_state_dict(sd)
+    hidden = 8 if net == "gat3" else 32
+    sd = {}
+    for i, k in ((1, 7), (2, hidden), (3, hidden))[:3 if net == "gat3" else 1]:
+        sd[f"conv{i}.att_src"] = glorot((1, 1, hidden), 1, hidden)
+        sd[f"conv{i}.att_dst"] = glorot((1, 1, hidden), 1, hidden)
+        sd[f"conv{i}.bias"] = torch.zeros(hidden)
+        sd[f"conv{i}.lin.weight"] = glorot((hidden, k), k, hidden)
+    sd["lin1.weight"], sd["lin1.bias"] = linear(hidden, hidden)
+    sd["lin2.weight"], sd["lin2.bias"] = linear(9, hidden)
+    return flatten_state_dict(sd, net=net)
 
 
 class SwarmEngine:
+    # a subclass that trains the three-layer network (SwarmGat3Engine) passes the learn=True refusal
+    trains_gat3 = False
+
     def __init__(self, scenario="GoTo", n_agents: int = 8, n_envs: int = 1024, *, seed: int = 0,
                  graph: str = "complete", knn_k: int = 10, conv: str = "gat", params=None, radius: float = 0.3,
                  batch: Optional[int] = None, gamma: float = 0.99, lr: float = 1e-3, betas=(0.9, 0.999),
@@ -119,9 +128,10 @@ class SwarmEngine:
             raise RuntimeError("SwarmEngine runs on a ROCm GPU only (no CPU fallback)")
         sid = SCENARIOS[scenario] if isinstance(scenario, str) else int(scenario)
         flags = (_lib.F_SHARED_RESET if shared_reset else 0) | (_lib.F_RANDOM_OA if random_oa else 0)
-        if net == "gat3" and learn:
+        if net == "gat3" and learn and not self.trains_gat3:
             raise ValueError("net='gat3' (the Flocking checkpoints' three-layer GAT) is not trained by the engine: use "
-                             "learn=False (GAT3(autograd=True) is its differentiable class)")
+                             "learn=False, or SwarmGat3Engine, its learner (GAT3(autograd=True) is its "
+                             "differentiable class)")
         self.net = net
         self.cfg = SwarmConfig(n_envs, n_agents, sid, GRAPHS[graph], knn_k, CONVS[conv], env_offset, flags,
                                seed & 0xFFFFFFFFFFFFFFFF, float(radius), NETS[net])
@@ -147,10 +157,10 @@ class SwarmEngine:
                                if nst > n_envs * n_agents * 4 else None)
         n_par = _lib.GAT3_N_PARAMS if net == "gat3" else N_PARAMS
         if params is None:
-            if net == "gat3":
+            if net == "gat3" and not self.trains_gat3:
                 raise ValueError("net='gat3' needs params (a Flocking checkpoint)")
             g = torch.Generator().manual_seed(seed)
-            params = glorot_init(g)
+            params = glorot_init(g, net)
         elif isinstance(params, dict):
             params = flatten_state_dict(params, net=net)
         p0 = params.detach().to(**f32).reshape(-1)
@@ -173,7 +183,8 @@ class SwarmEngine:
         self.rep_r = torch.zeros(cap, n_envs, n_agents, **f32)
         self.rep_a = torch.zeros(cap, n_envs, n_agents, dtype=torch.uint8, device=dev)
         self.replay = SwarmReplay(ptr(self.rep_s), ptr(self.rep_s1), ptr(self.rep_r), ptr(self.rep_a), cap, 0)
-        ws = _lib.size(self.lib, "swarm_td_workspace_floats", self.cfg, self.batch) if net == "gcn" else 4
+        ws = (_lib.size(self.lib, "swarm_td_workspace_floats", self.cfg, self.batch)
+              if net == "gcn" or self.trains_gat3 else 4)
         self.fused = learn and bool(self.lib.swarm_train_tick_supported(_lib.ref(self.cfg)))
         self.slabs = torch.zeros(ws, **f32)
         # + the reduce's norm partials (ABI 10); a write to grad from outside the library's reduce
@@ -416,6 +427,69 @@ class SwarmEngine:
     def load_state_dict(self, sd):
         self.params.copy_(flatten_state_dict(sd, net=self.net).to(self.device))
         self.target.copy_(self.params)
+
+
+class SwarmGat3Engine(SwarmEngine):
+    """The learner of the three-layer GAT (``net="gat3"``, the Flocking checkpoints' network, 409
+    parameters) on the unfused device path.  One training tick is four launches, all on torch's
+    current stream and capturable:
+
+        swarm_act_step        graph -> GAT3 Q -> eps-greedy -> env.step -> replay push   (1 launch)
+        swarm_gat3_td_grad    batch rows -> target fwd on s' -> online fwd on s -> TD loss ->
+                              backward, one wave per sampled graph; deterministic slab sum (2 launches)
+        swarm_gat3_adam_step  clip_grad_norm_ + Adam + target sync + ctrl advance        (1 launch)
+
+    The optimizer step is applied at once, so nothing is ever pending and ``flush()`` does nothing.
+    ``params`` is a flat tensor, a state dict, or None: a fresh ``glorot_init(seed, "gat3")``.
+    ``samples`` receives each tick's batch indices.  Limits of this class: no fused tick
+    (``train_tick3`` / ``launch_tick`` / ``launch_train_act``), no population, one rank
+    (``world_size`` = 1, no ``peer``), GATConv only."""
+    trains_gat3 = True
+
+    def __init__(self, scenario="Flocking", n_agents: int = 8, n_envs: int = 1024, **kw):
+        if kw.setdefault("net", "gat3") != "gat3":
+            raise ValueError("SwarmGat3Engine trains net='gat3' only (SwarmEngine trains the one-layer network)")
+        if kw.get("world_size", 1) != 1 or kw.get("peer") is not None or kw.get("process_group") is not None:
+            raise ValueError("SwarmGat3Engine runs on one rank: world_size = 1, no peer exchange, no process group")
+        if kw.get("conv", "gat") != "gat":
+            raise ValueError("SwarmGat3Engine: the three-layer network is a GAT (conv='gat')")
+        super().__init__(scenario, n_agents, n_envs, **kw)
+
+    def td_grad(self, sample_in: Optional[torch.Tensor] = None, sample_out: Optional[torch.Tensor] = None):
+        # the slabs and ``samples`` were sized for the batch the engine was built with
+        if not 1 <= self.hp.batch <= self.batch:
+            raise ValueError(f"hp.batch = {self.hp.batch}: this engine's buffers hold a batch of at most {self.batch}")
+        for name, t in (("sample_in", sample_in), ("sample_out", sample_out)):
+            if t is not None and t.numel() < self.hp.batch:
+                raise ValueError(f"{name} holds {t.numel()} indices for a batch of {self.hp.batch}")
+        call(self.lib, "swarm_gat3_td_grad", self.cfg, self.hp, ptr(self.params), ptr(self.target), self.replay,
+             ptr(self.ctrl), ptr(sample_in), ptr(sample_out), ptr(self.slabs), ptr(self.grad))
+
+    def adam(self):
+        call(self.lib, "swarm_gat3_adam_step", self.cfg, self.hp, ptr(self.params), ptr(self.target),
+             ptr(self.adam_m), ptr(self.adam_v), ptr(self.grad), self.capacity, ptr(self.ctrl))
+
+    def flush(self):
+        """Nothing is ever pending: ``adam`` applies each step at once."""
+
+    def td_update(self, sample_in=None, sample_out=None):
+        """TD update: gradient (2 launches), then the optimizer step.  The batch indices go to
+        ``sample_out``, or to ``self.samples`` when the kernel draws them itself."""
+        if sample_out is None and sample_in is None:
+            sample_out = self.samples
+        self.td_grad(sample_in, sample_out)
+        self.adam()
+
+    def train_tick(self, full_out: bool = False):
+        """The training tick of this network: act + push, TD gradient, optimizer step (4 launches)."""
+        self.train_tick_unfused(full_out)
+
+    def _no_fused(self, *args, **kw):
+        raise ValueError("SwarmGat3Engine has the unfused tick only (train_tick = train_tick_unfused: swarm_act_step, "
+                         "swarm_gat3_td_grad, swarm_gat3_adam_step); the fused and 3-launch ticks, populations and "
+                         "world_size > 1 train the one-layer network")
+
+    train_tick3 = launch_tick = launch_train_act = launch_td = launch_grad_reduce = launch_reduce_advance = _no_fused
 
 
 # the optimizer hyper-parameters a learner can change after it is built (SwarmEngine.set_hp) and a

@@ -22,7 +22,9 @@ lin1 -> relu -> lin2, hidden 8 — the architecture of the reference's Flocking 
 (``data/models/experiment_Flocking-seed_*.pth``, ``SWARM_NET_GAT3``).  ``GAT3`` is that network as
 a class of its own, and the one that takes ``autograd=True``: ``loss.backward()`` then runs one
 ``swarm_gat3_q_backward`` call, with the semantics above (Q bitwise the inference forward's, no
-gradient for ``data.x``).  ``DQNTrainer``, the engine and the fused tick do not train it.
+gradient for ``data.x``).  On the device it is trained by ``SwarmGat3Engine`` (engine.py) and
+``DQNTrainer(..., net="gat3")``, whose ``model`` / ``target_model`` are ``GAT3`` objects; the fused
+tick and populations do not train it.
 ``GCN.from_state_dict(sd)`` picks the architecture from the checkpoint's keys (a ``GAT3`` for a
 checkpoint that holds conv2).
 """

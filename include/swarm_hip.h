@@ -38,9 +38,11 @@ enum swarm_conv { SWARM_CONV_GAT = 0, SWARM_CONV_GCN = 1 };
 /* Q-network: GCN = the reference's GCN class (one GATConv, hidden 32; params N_PARAMS = 1673;
    trainable).  GAT3 = the same class with its commented conv2/conv3 layers (train_gcn_dqn.py:54-55,
    65-68), hidden 8, 409 params: what data/models/experiment_Flocking-seed_*.pth hold.  GAT3 runs
-   forward (swarm_q_forward, swarm_act_step, swarm_rollout) and has the backward for a caller's
-   dL/dQ (swarm_gat3_q_backward); the learner entry points (TD kernel, fused tick, populations)
-   and swarm_q_backward return SWARM_E_UNSUPPORTED for it. */
+   forward (swarm_q_forward, swarm_act_step, swarm_rollout), has the backward for a caller's
+   dL/dQ (swarm_gat3_q_backward) and trains on the unfused device path through entry points of
+   its own (swarm_act_step with a replay, swarm_gat3_td_grad, swarm_gat3_adam_step); the one-layer
+   network's learner entry points (swarm_td_grad, swarm_adam_step, fused tick, populations) and
+   swarm_q_backward return SWARM_E_UNSUPPORTED for it. */
 enum swarm_net { SWARM_NET_GCN = 0, SWARM_NET_GAT3 = 1 };
 #define SWARM_GAT3_N_PARAMS 409
 
@@ -258,6 +260,48 @@ int swarm_q_backward(const swarm_config* cfg, const float* params, const float* 
 #define SWARM_GAT3_GRAD_FLOATS 416   /* 409 gradients, then zeros */
 int swarm_gat3_q_backward(const swarm_config* cfg, const float* params, const float* x, const uint8_t* mult,
                           const float* dq, float* workspace, float* grad, void* stream);
+
+/* ---- The learner of SWARM_NET_GAT3 on the unfused device path (train_gcn_dqn.py:112-137 for the
+ * three-layer network): per tick swarm_act_step (with the replay) -> swarm_gat3_td_grad ->
+ * swarm_gat3_adam_step, four launches, what swarm_act_step -> swarm_td_grad -> swarm_grad_reduce ->
+ * swarm_adam_step is for the one-layer network.  The fused tick, populations and world_size > 1 stay
+ * that network's.
+ *
+ * swarm_gat3_td_grad: TD-loss gradient of a batch, the TD kernel + the slab sum, two launches.
+ * Batch position i takes graph sample_in[i] (clamped to capacity * n_envs - 1) or, with sample_in
+ * NULL, the graph swarm_td_grad would draw for it (the same keyed permutation of the
+ * min(filled_slots + 1, capacity) * n_envs graphs in the ring, keyed by ctrl->tick); sample_out
+ * [batch], if given, receives the ids.  One wave per graph: the target forward on s' (graph built
+ * from the positions of s') gives y = r + gamma max_a Q_target, the online forward on s (graph from
+ * s) gives td = Q[a] - y, and the backward of swarm_gat3_q_backward runs on dq = 2 td / (batch N)
+ * at the taken action (MSELoss mean).  grad [SWARM_GAT3_GRAD_FLOATS]: [0, 409) the gradient in the
+ * checkpoint's flat order, [409] the batch's sum of squared TD errors, [410..415] = 0.  While the
+ * ring holds fewer than `batch` graphs the call writes grad = 0 (every slab column too) and
+ * nothing else.  params / target hold 409 weights (SWARM_GAT3_GRAD_FLOATS floats where
+ * swarm_gat3_adam_step takes them too).
+ * workspace: swarm_td_workspace_floats(cfg, hp->batch) floats, need not be zeroed.
+ * No atomics: bitwise reproducible.  No allocation, no host sync: capturable.
+ *
+ * swarm_gat3_adam_step: clip_grad_norm_(hp->max_norm) + Adam + target sync (when (tick + 1) %
+ * update_target_every == 0) on the 409 parameters, then the control block advanced, in one launch:
+ * swarm_adam_step's semantics field for field (the step runs iff min(filled_slots + 1,
+ * replay_capacity) * n_envs >= batch; loss = grad[409] / (batch N) or 0; grad_norm or 0; trained
+ * = 0; adam_step, the beta powers and the next step's scalars advanced when it ran; tick + 1,
+ * write_slot advanced, filled_slots).  params, target, adam_m, adam_v hold SWARM_GAT3_GRAD_FLOATS
+ * floats each; floats 409..415 are never used for a weight and are left as they are.
+ *
+ * Checks of both, in this order, all before any launch: the configuration and hp as swarm_td_grad /
+ * swarm_adam_step check them (SWARM_E_BADARG / SWARM_E_KNN_K; GAT3 with GCNConv: SWARM_E_BADARG);
+ * net != SWARM_NET_GAT3: SWARM_E_UNSUPPORTED; hp->world_size != 1: SWARM_E_UNSUPPORTED;
+ * SWARM_GRAPH_DENSE: SWARM_E_BADARG (as for every TD entry point); a NULL pointer other than
+ * sample_in / sample_out (the replay's four arrays among them), or a capacity < 1: SWARM_E_BADARG.
+ * (tests/test_gat3_td_host.py, tests/test_gpu_gat3_td.py) */
+int swarm_gat3_td_grad(const swarm_config* cfg, const swarm_adam_cfg* hp, const float* params, const float* target,
+                       const swarm_replay* replay, const swarm_ctrl* ctrl, const int32_t* sample_in,
+                       int32_t* sample_out, float* workspace, float* grad, void* stream);
+int swarm_gat3_adam_step(const swarm_config* cfg, const swarm_adam_cfg* hp, float* params, float* target,
+                         float* adam_m, float* adam_v, const float* grad, int32_t replay_capacity,
+                         swarm_ctrl* ctrl, void* stream);
 
 /* Fused acting tick (train_gcn_dqn.py:161-172 / simulator.py:59-68):
  * graph -> GAT Q -> eps-greedy (ctrl->eps, Philox) -> env.step -> replay push

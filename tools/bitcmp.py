@@ -9,7 +9,8 @@ leave every bit alone).  The kinds of case:
          control block;
   td   : the unfused swarm_td_grad on a seeded replay (tests/test_gpu_parity.py _fill_replay) and a
          fixed sample_in; the gradient buffer;
-  qb   : swarm_q_backward on a case of tests/test_q_backward.py; the whole gradient buffer.
+  qb   : swarm_q_backward on a case of tests/test_q_backward.py; the whole gradient buffer;
+  g3b  : swarm_gat3_q_backward on a case of tests/test_gat3_backward.py; its 416-float gradient buffer.
 
 usage: python tools/bitcmp.py LIB_A LIB_B [scenario N B ticks]    one tick case (LIB = base or a path)
        python tools/bitcmp.py LIB_A LIB_B --matrix [OUT.jsonl]    MATRIX: every instance of the TD
@@ -24,7 +25,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-# (kind, ...): tick: scenario, N, envs, ticks, graph, conv; td: scenario, N, S, graph, k, conv; qb: case index
+# (kind, ...): tick: scenario, N, envs, ticks, graph, conv; td: scenario, N, S, graph, k, conv; qb, g3b: case index
 MATRIX = (
     [("tick", scen, N, B, 6, "complete", conv)
      for scen, N, B in (("GoTo", 5, 64),                 # two 8-slot graphs per wave, padded slots
@@ -35,6 +36,7 @@ MATRIX = (
     + [("td", "ObstacleAvoidance", N, 5, "complete", 0, conv) for N in (20, 29) for conv in ("gat", "gcn")]
     + [("td", "ObstacleAvoidance", 12, 5, "knn", 5, "gat")]
     + [("qb", i) for i in range(17)]
+    + [("g3b", i) for i in range(13)]                    # every slot class, graph kind and the two-slab reduce groups
     + [("tick", scen, N, B, 6, "complete", "gat")        # the benchmark's sizes
        for scen, N, B in (("GoTo", 8, 1024), ("ObstacleAvoidance", 12, 1024), ("ObstacleAvoidance", 5, 512),
                           ("ObstacleAvoidance", 12, 512))]
@@ -80,6 +82,12 @@ def run_case(case):
         eng.td_grad(sample_in=idx.cuda())
         torch.cuda.synchronize()
         return {"grad": eng.grad.cpu()}, eng.handoff_errors()
+    if kind == "g3b":
+        from tests import test_gat3_backward as T
+        N, B, graph, k, seed, holes = T.CASES[case[1]]
+        s, x, mult, dq = T._case_inputs(N, B, graph, k, holes)
+        p = torch.tensor(np.load(os.path.join(ROOT, "tests", "golden", "flocking_weights.npz"))["weights_flocking"][seed])
+        return {"grad": T._Call(N, B, graph, k, p, x, mult, dq).run()}, 0
     from tests.test_q_backward import CASES, _case_inputs, _q_backward
     scen, N, B, graph, k, conv, holes = CASES[case[1]]
     s, x, mult, dq = _case_inputs(N, B, graph, k, holes)
