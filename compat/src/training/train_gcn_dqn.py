@@ -5,6 +5,8 @@ the reference's scripts import from it, backed by the MI355X path.
     GAT3                 the same class with its commented conv2 / conv3 layers (:54-55, :65-68), hidden 8:
                          the Flocking checkpoints' network, differentiable with autograd=True
     SwarmGat3Engine      the device learner of GAT3 (DQNTrainer(..., net="gat3") drives it)
+    SwarmGat3Population  many of them (the ten Flocking seeds) ticked together; Gat3PopulationTrainer drives
+                         it for several DQNTrainer(..., net="gat3")
     GraphReplayBuffer    :25-48
     DQNTrainer           :72-231  (create_graph_from_observations, train_step_dqn, train_model,
                                    save_metrics_to_csv; the episode loop runs fused on the GPU;
@@ -23,10 +25,10 @@ _ROOT = _os.path.dirname(_os.path.dirname(_os.path.dirname(_os.path.dirname(_os.
 if _ROOT not in _sys.path:
     _sys.path.append(_ROOT)
 
-from swarm_amd import (GAT3, GCN, DQNTrainer, GraphReplayBuffer, SwarmGat3Engine, get_scenario, make_env,  # noqa: E402,F401
-                       set_seed)
+from swarm_amd import (GAT3, GCN, DQNTrainer, Gat3PopulationTrainer, GraphReplayBuffer, SwarmGat3Engine,  # noqa: E402,F401
+                       SwarmGat3Population, get_scenario, make_env, set_seed)
 
-__all__ = ["GCN", "GAT3", "SwarmGat3Engine", "DQNTrainer", "GraphReplayBuffer", "set_seed", "get_scenario", "main"]
+__all__ = ["GCN", "GAT3", "SwarmGat3Engine", "SwarmGat3Population", "Gat3PopulationTrainer", "DQNTrainer", "GraphReplayBuffer", "set_seed", "get_scenario", "main"]
 
 
 def main(max_seed=10, experiments=("ObstacleAvoidance", "GoTo"), agents=10, episodes=1000,

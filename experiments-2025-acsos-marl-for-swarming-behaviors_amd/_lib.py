@@ -75,6 +75,15 @@ class SwarmPopActor(ctypes.Structure):
                 ("tick0", c_uint32), ("eps", c_float)]
 
 
+class SwarmGat3Member(ctypes.Structure):
+    """One member of a population of three-layer GAT learners (swarm_gat3_member): what swarm_act_step,
+    swarm_gat3_td_grad and swarm_gat3_adam_step take for a lone learner.  The array of them lives in
+    device memory (population.SwarmGat3Population)."""
+    _fields_ = [("seed", c_uint64), ("state", c_void_p), ("replay", SwarmReplay), ("params", c_void_p),
+                ("target", c_void_p), ("adam_m", c_void_p), ("adam_v", c_void_p), ("grad", c_void_p),
+                ("ctrl", c_void_p), ("out", SwarmActOut), ("slabs", c_void_p), ("sample_out", c_void_p)]
+
+
 PBT_F_LR, PBT_F_GAMMA = 1, 2   # swarm_pbt_cfg.fields
 PBT_MAX_MEMBERS = 1024         # SWARM_PBT_MAX_MEMBERS
 STREAM_PBT = 5                 # third Philox counter word of the PBT draws (csrc/swarm_pbt.h)
@@ -167,6 +176,13 @@ _PROTOS = {
                                               c_int32, c_stream]),
     # (cfg, actors table [P] of SwarmPopActor in device memory, P, n_ticks, stream)
     "swarm_pop_rollout": (c_int32, [POINTER(SwarmConfig), c_void_p, c_int32, c_int32, c_stream]),
+    # (cfg, members table [P] of SwarmGat3Member in device memory, P, stream)
+    "swarm_pop_gat3_act_step": (c_int32, [POINTER(SwarmConfig), c_void_p, c_int32, c_stream]),
+    # (cfg, shared hp, member_hp table [P] of SwarmAdamCfg in device memory or NULL, members table, P, stream)
+    "swarm_pop_gat3_td_grad": (c_int32, [POINTER(SwarmConfig), POINTER(SwarmAdamCfg), c_void_p, c_void_p, c_int32,
+                                         c_stream]),
+    "swarm_pop_gat3_adam_step": (c_int32, [POINTER(SwarmConfig), POINTER(SwarmAdamCfg), c_void_p, c_void_p, c_int32,
+                                           c_stream]),
     # (pbt, score [P] float, member_hp table, members table, P, parent [P] int32: all device memory; stream)
     "swarm_pop_exploit": (c_int32, [POINTER(SwarmPbtCfg), c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_stream]),
     "swarm_peer_buffer_bytes": (c_int64, []),
@@ -185,7 +201,8 @@ EXPORTED = tuple(_PROTOS)
 # added under ABI 10 after other additions: a library of an earlier build of the same ABI (the A / B
 # side of tools/bitcmp.py, SWARM_LIB_PATH) lacks it and still loads; calling it there raises.  The
 # in-tree library must have every symbol (__graft_entry__.build, tests/test_cpu_host.py).
-_NEWEST = ("swarm_gat3_q_backward", "swarm_gat3_td_grad", "swarm_gat3_adam_step")
+_NEWEST = ("swarm_gat3_q_backward", "swarm_gat3_td_grad", "swarm_gat3_adam_step", "swarm_pop_gat3_act_step",
+           "swarm_pop_gat3_td_grad", "swarm_pop_gat3_adam_step")
 
 _lib = None
 

@@ -10,7 +10,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SOURCES = ["swarm_act.hip", "swarm_td.hip", "swarm_tick.hip", "swarm_peer.hip", "swarm_qbk.hip", "swarm_gat3_bwd.hip", "swarm_gat3_td.hip", "swarm_pop.hip",
-           "swarm_pop_hp.hip", "swarm_pop_rollout.hip", "swarm_pop_pbt.hip"]
+           "swarm_pop_hp.hip", "swarm_pop_rollout.hip", "swarm_pop_pbt.hip", "swarm_pop_gat3.hip"]
 HEADERS = ["swarm_actk.h", "swarm_tdk.h", "swarm_bwd.h", "swarm_common.h", "swarm_knn.h", "swarm_wpg.h", "swarm_dl.h", "swarm_env.h",
            "swarm_adam.h", "swarm_gat3.h", "swarm_peer.h", "swarm_launch.h", "swarm_diag.h", "swarm_qbk.h", "swarm_reduce.h",
            "swarm_reduce_body.h", "swarm_popk.h", "swarm_pop_tick_body.h",

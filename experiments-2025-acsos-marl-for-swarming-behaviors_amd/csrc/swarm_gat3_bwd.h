@@ -527,33 +527,51 @@ constexpr int kG3RedBlocks = kG3Cols / kG3RedCols;
 
 // LOSS = 1 (the TD path, swarm_gat3_td.h): column 409, the batch's sum of squared TD errors, is
 // carried through as well; 0: grad[409..415] = 0
+struct G3RedArgs {
+  const float* slabs;   // [n_slabs][kG3Cols]
+  int n_slabs;
+  float* grad;          // [kG3Cols]
+};
+struct G3RedSmem {
+  float part[kG3RedGroups][kG3RedCols];
+  float part2[kG3RedGroups / 8][kG3RedCols];
+};
+// column block bx of the slab sum: gat3_grad_reduce_kernel's block, and block (bx, m) of the
+// population's (swarm_pop_gat3.hip) with member m's slabs and grad in A
 template <int LOSS>
-__global__ __launch_bounds__(kG3RedCols * kG3RedGroups) void gat3_grad_reduce_kernel(const float* __restrict__ slabs,
-                                                                                    int n_slabs,
-                                                                                    float* __restrict__ grad) {
-  __shared__ float part[kG3RedGroups][kG3RedCols];
-  __shared__ float part2[kG3RedGroups / 8][kG3RedCols];
+__device__ __forceinline__ void g3_reduce_block(G3RedSmem& L, const int bx, const G3RedArgs& A) {
+  const float* __restrict__ slabs = A.slabs;
+  float* __restrict__ grad = A.grad;
+  const int n_slabs = A.n_slabs;
   const int c = threadIdx.x % kG3RedCols, q = threadIdx.x / kG3RedCols;
-  const int col = blockIdx.x * kG3RedCols + c;
+  const int col = bx * kG3RedCols + c;
   const int per = (n_slabs + kG3RedGroups - 1) / kG3RedGroups;
   const int b0 = min(n_slabs, q * per), b1 = min(n_slabs, b0 + per);
   float s = 0.0f;
   for (int b = b0; b < b1; ++b) s = s + slabs[(size_t)b * kG3Cols + col];
-  part[q][c] = s;
+  L.part[q][c] = s;
   __syncthreads();
   if (q < kG3RedGroups / 8) {
-    float r = part[8 * q][c];
+    float r = L.part[8 * q][c];
 #pragma unroll
-    for (int gi = 1; gi < 8; ++gi) r = r + part[8 * q + gi][c];
-    part2[q][c] = r;
+    for (int gi = 1; gi < 8; ++gi) r = r + L.part[8 * q + gi][c];
+    L.part2[q][c] = r;
   }
   __syncthreads();
   if (q == 0) {
-    float tot = part2[0][c];
+    float tot = L.part2[0][c];
 #pragma unroll
-    for (int gi = 1; gi < kG3RedGroups / 8; ++gi) tot = tot + part2[gi][c];
+    for (int gi = 1; gi < kG3RedGroups / 8; ++gi) tot = tot + L.part2[gi][c];
     grad[col] = col < G3_N_PARAMS + LOSS ? tot : 0.0f;
   }
+}
+
+template <int LOSS>
+__global__ __launch_bounds__(kG3RedCols * kG3RedGroups) void gat3_grad_reduce_kernel(const float* __restrict__ slabs,
+                                                                                    int n_slabs,
+                                                                                    float* __restrict__ grad) {
+  __shared__ G3RedSmem L;
+  g3_reduce_block<LOSS>(L, blockIdx.x, G3RedArgs{slabs, n_slabs, grad});
 }
 
 // The two launches (swarm_gat3_bwd.hip).  The kernels are instantiated in a translation unit of

@@ -38,6 +38,7 @@
 #pragma once
 #include "swarm_adam.h"
 #include "swarm_gat3_bwd.h"
+#include "swarm_launch.h"
 
 namespace swarm {
 
@@ -176,11 +177,12 @@ __device__ __forceinline__ void g3t_wave(const float* __restrict__ Pon, const fl
   g3b_backward<NS>(Pon, W, part, G, K, dqv);
 }
 
+// TD block bx of a batch: gat3_td_kernel's block, and block (bx, m) of the population's
+// (swarm_pop_gat3.hip) with member m's keys, weights, ring, ctrl, slabs and sample_out in A
 template <int NS>
-__global__ __launch_bounds__(64 * g3b_waves(NS)) void gat3_td_kernel(G3tArgs A) {
+__device__ __forceinline__ void g3t_block(G3tSmem<NS>& L, const int bx, const G3tArgs& A) {
   constexpr int WPB = g3b_waves(NS), NT = 64 * WPB;
-  __shared__ G3tSmem<NS> L;
-  float* slab = A.slabs + (size_t)blockIdx.x * kG3Cols;
+  float* slab = A.slabs + (size_t)bx * kG3Cols;
   const uint32_t cap = (uint32_t)A.replay.capacity;
   const uint32_t filled = A.ctrl->filled_slots;
   const uint32_t valid_slots = filled + 1 < cap ? filled + 1 : cap;
@@ -196,7 +198,7 @@ __global__ __launch_bounds__(64 * g3b_waves(NS)) void gat3_td_kernel(G3tArgs A) 
   }
   __syncthreads();   // weight images
   const int wi = threadIdx.x >> 6;
-  const int i = (int)blockIdx.x * WPB + wi;
+  const int i = (int)bx * WPB + wi;
   if (i < A.S) {
     uint32_t gid;
     if (A.sample_in) {   // clamped into the ring: a bad index reads valid rows
@@ -221,6 +223,12 @@ __global__ __launch_bounds__(64 * g3b_waves(NS)) void gat3_td_kernel(G3tArgs A) 
   }
 }
 
+template <int NS>
+__global__ __launch_bounds__(64 * g3b_waves(NS)) void gat3_td_kernel(G3tArgs A) {
+  __shared__ G3tSmem<NS> L;
+  g3t_block<NS>(L, blockIdx.x, A);
+}
+
 // ---------------------------------------------------------------- clip + Adam + target sync
 struct G3AdamArgs {
   swarm_adam_cfg hp;
@@ -240,8 +248,9 @@ static_assert(kG3NF4 == 104 && kG3FullF4 == 102 && 4 * kG3FullF4 + 1 == G3_N_PAR
               "a thread's float4 t; parameter 408 alone in float4 102");
 static_assert((kG3NF4 + 3) / 4 <= 32, "the norm's groups fit half a wave");
 
-__global__ __launch_bounds__(kG3AdamNT) void gat3_adam_kernel(G3AdamArgs A) {
-  __shared__ float red[32];
+// the one block of the optimizer step: gat3_adam_kernel's, and block (0, m) of the population's
+// (swarm_pop_gat3.hip) with member m's rows, ctrl, ring capacity and optimizer row in A; red: 32 floats of LDS
+__device__ __forceinline__ void g3_adam_block(float* red, const G3AdamArgs& A) {
   const int tid = threadIdx.x;
   const int f4 = min(tid, kG3NF4 - 1);
   float4 g = reinterpret_cast<const float4*>(A.grad)[f4];
@@ -317,5 +326,15 @@ __global__ __launch_bounds__(kG3AdamNT) void gat3_adam_kernel(G3AdamArgs A) {
 // own, for swarm_gat3_bwd.hip's reason: no other kernel's code may depend on them.
 __attribute__((visibility("hidden"))) int gat3_td_launch(const G3tArgs& A, hipStream_t stream);
 __attribute__((visibility("hidden"))) int gat3_adam_launch(const G3AdamArgs& A, hipStream_t stream);
+
+// the checks swarm_gat3_td_grad / swarm_gat3_adam_step and the population's pair (swarm_pop_gat3.hip)
+// share, in swarm_hip.h's order
+inline int check_gat3_td(const swarm_config* c, const swarm_adam_cfg* hp) {
+  if (int e = check_config(c, kCfgGat3Td, hp)) return e;
+  if (c->net != SWARM_NET_GAT3) return SWARM_E_UNSUPPORTED;   // the one-layer network: swarm_td_grad / swarm_adam_step
+  if (hp->world_size != 1) return SWARM_E_UNSUPPORTED;
+  if (c->graph == SWARM_GRAPH_DENSE) return SWARM_E_BADARG;
+  return 0;
+}
 
 }  // namespace swarm

@@ -16,6 +16,12 @@ constexpr bool g3t_slabs_fit(int gs) {
 static_assert(g3t_slabs_fit(8) && g3t_slabs_fit(16) && g3t_slabs_fit(32), "gat3 TD slabs fit the TD workspace");
 static_assert(kG3Cols == SWARM_GAT3_GRAD_FLOATS && G3_N_PARAMS == SWARM_GAT3_N_PARAMS, "header");
 
+// no template: defined here, once, not in the header swarm_pop_gat3.hip includes too
+__global__ __launch_bounds__(kG3AdamNT) void gat3_adam_kernel(G3AdamArgs A) {
+  __shared__ float red[32];
+  g3_adam_block(red, A);
+}
+
 // gat3_td_kernel<NS> (the graph is read at run time, as in every GAT3 kernel), then the slab sum
 // with the loss column
 int gat3_td_launch(const G3tArgs& A, hipStream_t stream) {
@@ -37,17 +43,6 @@ int gat3_adam_launch(const G3AdamArgs& A, hipStream_t stream) {
 }  // namespace swarm
 
 using namespace swarm;
-
-namespace {
-// the checks both entry points share, in the header's order
-int check_gat3_td(const swarm_config* c, const swarm_adam_cfg* hp) {
-  if (int e = check_config(c, kCfgGat3Td, hp)) return e;
-  if (c->net != SWARM_NET_GAT3) return SWARM_E_UNSUPPORTED;   // the one-layer network: swarm_td_grad / swarm_adam_step
-  if (hp->world_size != 1) return SWARM_E_UNSUPPORTED;
-  if (c->graph == SWARM_GRAPH_DENSE) return SWARM_E_BADARG;
-  return 0;
-}
-}  // namespace
 
 extern "C" {
 

@@ -13,7 +13,8 @@ hipGraph and replayed.
 ``SwarmGat3Engine``): the same loop, each tick four launches (act + push, TD gradient, optimizer step)
 instead of the fused two, captured and replayed the same way; the saved ``.pth`` has that network's
 keys.  Whether a tick ran an update is taken from ``ctrl.adam_step`` advancing (its optimizer step is
-applied at once, so ``trained`` stays 0).  Such a trainer cannot join a ``PopulationTrainer``.
+applied at once, so ``trained`` stays 0).  Such trainers form a ``Gat3PopulationTrainer`` (a
+``SwarmGat3Population``: all of them in the four launches per tick of one), not a ``PopulationTrainer``.
 
 Optional evaluation inside training (not in the reference, whose training loop never evaluates):
 with ``config["eval_every"] = E`` every E-th episode ends with a greedy rollout of the current
@@ -49,7 +50,7 @@ from . import _lib
 from .engine import SwarmEngine, SwarmGat3Engine, flatten_state_dict, glorot_init, unflatten_params
 from .gcn import GAT3, GCN
 from .graph import Batch, Data, create_graph_from_observations
-from .population import SwarmPopulation, evaluation_engine
+from .population import SwarmGat3Population, SwarmPopulation, evaluation_engine
 
 
 class SummaryWriter:
@@ -256,7 +257,64 @@ class DQNTrainer:
                     w.writerow([i, float(self.episode_rewards[i // 10]), self.episode_losses[i // 10]])
 
 
-class PopulationTrainer:
+class _PopulationDriver:
+    """What ``PopulationTrainer`` and ``Gat3PopulationTrainer`` share: the trainers' engines re-homed
+    into one population of ``population_class``, the per-tick bookkeeping on [P] device tensors, the
+    evaluation of all members in one launch and the loop."""
+    net = "gcn"
+    population_class = SwarmPopulation
+    refusal = ""
+
+    def __init__(self, trainers):
+        self.trainers = list(trainers)
+        first = self.trainers[0]
+        if any(t.net != self.net for t in self.trainers):
+            raise ValueError(self.refusal)
+        for t in self.trainers:
+            if (t.env.max_steps, t.env.n_agents, t.use_graph) != (first.env.max_steps, first.env.n_agents,
+                                                                   first.use_graph):
+                raise ValueError("the trainers of a population share max_steps, n_agents and use_graph")
+        self.population = self.population_class.from_engines([t.engine for t in self.trainers])
+
+    def _episode_fn(self, max_steps: int):
+        """DQNTrainer._episode_fn for every member at once: the same per-tick bookkeeping, on
+        [P]-shaped device tensors (a fixed number of launches whatever P is)."""
+        pop = self.population
+        n = self.trainers[0].env.n_agents
+        ctrl_f = pop.ctrl.view(torch.float32)
+        calls = [0]
+        # the unfused optimizer step (net="gat3") leaves `trained` 0: an update ran iff adam_step advanced
+        unfused = self.net == "gat3"
+        step = pop.ctrl[:, _lib.CTRL["adam_step"]]
+        step_before = torch.zeros(pop.P, dtype=torch.int32, device=pop.device)
+
+        def tick():
+            i = calls[0] % max_steps
+            calls[0] += 1
+            if unfused:
+                step_before.copy_(step)
+            pop.train_tick(full_out=False)
+            self._acc_reward.add_(pop.reward[:, :, 0].mean(dim=1) / n)
+            self._acc_loss.add_(ctrl_f[:, 5])
+            self._tick_reward[i].copy_(pop.reward.sum(dim=2).mean(dim=1))
+            self._tick_loss[i].copy_(ctrl_f[:, 5])
+            self._tick_trained[i].copy_(step - step_before if unfused else pop.ctrl[:, 7])
+        return tick
+
+    def _evaluate(self, ev: dict, n_ticks: int):
+        """Every member's evaluation in one launch (DQNTrainer._evaluate's rows, member by member)"""
+        res = self.population.evaluate(ev["envs"], n_ticks, seed=ev["seed"], episode=0, graph=ev["graph"],
+                                       knn_k=ev["knn_k"])
+        self._eval_reward = res["reward"]   # [P, envs, N] on the device: what a PBT round scores
+        res = {k: v.cpu() for k, v in res.items()}
+        return [{k: v[m] for k, v in res.items()} for m in range(self.population.P)]
+
+    def train_model(self, config):
+        _train_loop(self, self.population, self.trainers, (self.population.P,), config, "Seed {seed}, ",
+                    "Models saved successfully!")
+
+
+class PopulationTrainer(_PopulationDriver):
     """Several ``DQNTrainer`` objects over one scenario and agent count (the reference's seeds
     0-9 of one experiment, train_gcn_dqn.py:262-290) trained together: their engines become the
     members of one ``SwarmPopulation``, so a training tick of all of them is two launches.
@@ -269,48 +327,11 @@ class PopulationTrainer:
     then ticks with one optimizer row per member), and ``config``'s ``epsilon``, ``epsilon_decay`` and
     ``min_epsilon`` may each be a sequence of one value per trainer; they share ``batch_size``, the
     ring capacity and everything else of the configuration."""
-
-    def __init__(self, trainers):
-        self.trainers = list(trainers)
-        first = self.trainers[0]
-        if any(t.net != "gcn" for t in self.trainers):
-            raise ValueError("a population trains the one-layer network: DQNTrainer(net='gat3') trains alone "
-                             "(SwarmGat3Engine has the unfused tick only)")
-        for t in self.trainers:
-            if (t.env.max_steps, t.env.n_agents, t.use_graph) != (first.env.max_steps, first.env.n_agents,
-                                                                   first.use_graph):
-                raise ValueError("the trainers of a population share max_steps, n_agents and use_graph")
-        self.population = SwarmPopulation.from_engines([t.engine for t in self.trainers])
-
-    def _episode_fn(self, max_steps: int):
-        """DQNTrainer._episode_fn for every member at once: the same per-tick bookkeeping, on
-        [P]-shaped device tensors (a fixed number of launches whatever P is)."""
-        pop = self.population
-        n = self.trainers[0].env.n_agents
-        ctrl_f = pop.ctrl.view(torch.float32)
-        calls = [0]
-
-        def tick():
-            i = calls[0] % max_steps
-            calls[0] += 1
-            pop.train_tick(full_out=False)
-            self._acc_reward.add_(pop.reward[:, :, 0].mean(dim=1) / n)
-            self._acc_loss.add_(ctrl_f[:, 5])
-            self._tick_reward[i].copy_(pop.reward.sum(dim=2).mean(dim=1))
-            self._tick_loss[i].copy_(ctrl_f[:, 5])
-            self._tick_trained[i].copy_(pop.ctrl[:, 7])
-        return tick
+    refusal = ("a PopulationTrainer trains the one-layer network: DQNTrainer(net='gat3') objects form a "
+               "Gat3PopulationTrainer (SwarmGat3Engine has the unfused tick only)")
 
     def _check_episode(self):
         self.population.check_handoffs()
-
-    def _evaluate(self, ev: dict, n_ticks: int):
-        """Every member's evaluation in one launch (DQNTrainer._evaluate's rows, member by member)"""
-        res = self.population.evaluate(ev["envs"], n_ticks, seed=ev["seed"], episode=0, graph=ev["graph"],
-                                       knn_k=ev["knn_k"])
-        self._eval_reward = res["reward"]   # [P, envs, N] on the device: what a PBT round scores
-        res = {k: v.cpu() for k, v in res.items()}
-        return [{k: v[m] for k, v in res.items()} for m in range(self.population.P)]
 
     def _pbt_round(self, episode: int, rnd: int, kw: dict):
         """One exploit round scored by the evaluation just run: each member's reward summed over
@@ -324,9 +345,24 @@ class PopulationTrainer:
         for m, t in enumerate(self.trainers):
             t.pbt_rows.append((episode, parent[m], t.engine.hp.lr_d, t.engine.hp.gamma))
 
-    def train_model(self, config):
-        _train_loop(self, self.population, self.trainers, (self.population.P,), config, "Seed {seed}, ",
-                    "Models saved successfully!")
+
+class Gat3PopulationTrainer(_PopulationDriver):
+    """``PopulationTrainer`` for ``DQNTrainer(net="gat3")`` objects (the reference's Flocking
+    experiment: ten seeds, one environment each): their ``SwarmGat3Engine``s become the members of one
+    ``SwarmGat3Population``, so a training tick of all of them is the four launches one of them
+    costs.  ``train_model(config)`` leaves each trainer as its own ``train_model`` would: the same
+    lists, writer scalars, ``.pth`` and ``.csv`` / ``-eval.csv`` files; the second and later episodes
+    are captured; ``eval_every`` evaluates all members in one launch.  An update ran when
+    ``ctrl.adam_step`` advanced, as in the lone trainer.  The trainers may differ in ``lr``, ``gamma``
+    and ``update_target_every`` and the epsilon schedule may be per member, as ``PopulationTrainer``
+    documents.  There is no population-based training: ``pbt_every`` raises ValueError."""
+    net = "gat3"
+    population_class = SwarmGat3Population
+    refusal = ("a Gat3PopulationTrainer trains the three-layer network: DQNTrainer(net='gcn') objects form a "
+               "PopulationTrainer")
+
+    def _check_episode(self):
+        """the unfused tick has no hand-off to check"""
 
 
 def _is_sequence(v) -> bool:
@@ -383,8 +419,9 @@ def _train_loop(driver, group, trainers, shape, config, prefix: str, saved: str)
     pbt_every = pbt_schedule(config)
     if pbt_every is not None:
         if not hasattr(driver, "_pbt_round"):
-            raise ValueError("pbt_every needs a PopulationTrainer: a lone trainer has nobody to exploit (and "
-                             "DQNTrainer(net='gat3') cannot join one)")
+            raise ValueError("pbt_every needs a PopulationTrainer: a lone trainer has nobody to exploit, and "
+                             "population-based training works on the one-layer network's populations only (not on "
+                             "a Gat3PopulationTrainer)")
         group.per_member_hp = True   # before the episode is captured: the rows will change
     epsilon = initial_epsilon
     driver._acc_reward = torch.zeros(shape, device=group.device)

@@ -130,8 +130,8 @@ class SwarmEngine:
         flags = (_lib.F_SHARED_RESET if shared_reset else 0) | (_lib.F_RANDOM_OA if random_oa else 0)
         if net == "gat3" and learn and not self.trains_gat3:
             raise ValueError("net='gat3' (the Flocking checkpoints' three-layer GAT) is not trained by the engine: use "
-                             "learn=False, or SwarmGat3Engine, its learner (GAT3(autograd=True) is its "
-                             "differentiable class)")
+                             "learn=False, or SwarmGat3Engine, its learner (SwarmGat3Population: many of them; "
+                             "GAT3(autograd=True) is its differentiable class)")
         self.net = net
         self.cfg = SwarmConfig(n_envs, n_agents, sid, GRAPHS[graph], knn_k, CONVS[conv], env_offset, flags,
                                seed & 0xFFFFFFFFFFFFFFFF, float(radius), NETS[net])
@@ -442,8 +442,10 @@ class SwarmGat3Engine(SwarmEngine):
     The optimizer step is applied at once, so nothing is ever pending and ``flush()`` does nothing.
     ``params`` is a flat tensor, a state dict, or None: a fresh ``glorot_init(seed, "gat3")``.
     ``samples`` receives each tick's batch indices.  Limits of this class: no fused tick
-    (``train_tick3`` / ``launch_tick`` / ``launch_train_act``), no population, one rank
-    (``world_size`` = 1, no ``peer``), GATConv only."""
+    (``train_tick3`` / ``launch_tick`` / ``launch_train_act``), one rank (``world_size`` = 1, no
+    ``peer``), GATConv only.  Many of these learners tick together as a ``SwarmGat3Population``
+    (population.py: the same four launches for all of them); ``SwarmPopulation`` and its
+    population-based training stay the one-layer network's."""
     trains_gat3 = True
 
     def __init__(self, scenario="Flocking", n_agents: int = 8, n_envs: int = 1024, **kw):
@@ -486,8 +488,9 @@ class SwarmGat3Engine(SwarmEngine):
 
     def _no_fused(self, *args, **kw):
         raise ValueError("SwarmGat3Engine has the unfused tick only (train_tick = train_tick_unfused: swarm_act_step, "
-                         "swarm_gat3_td_grad, swarm_gat3_adam_step); the fused and 3-launch ticks, populations and "
-                         "world_size > 1 train the one-layer network")
+                         "swarm_gat3_td_grad, swarm_gat3_adam_step); the fused and 3-launch ticks, SwarmPopulation and "
+                         "world_size > 1 train the one-layer network (SwarmGat3Population ticks many of these "
+                         "learners together)")
 
     train_tick3 = launch_tick = launch_train_act = launch_td = launch_grad_reduce = launch_reduce_advance = _no_fused
 

@@ -29,6 +29,12 @@ Population-based training closes the loop on the device: ``SwarmPopulation.explo
 (swarm_pop_exploit) ranks the members by a device score, copies the best members' learners,
 optimizer state and hyper-parameter rows over the worst and perturbs the copies' lr / gamma, in two
 launches with no host round trip (tests/test_gpu_pop_pbt.py).
+
+The three-layer GAT (``net="gat3"``, the Flocking checkpoints' network) has a population of its own:
+``SwarmGat3Population`` ticks P ``SwarmGat3Engine`` learners in the four launches of that engine's
+unfused tick (swarm_pop_gat3_act_step / _td_grad / _adam_step, the member as the grid's second
+dimension), with the same per-member hyper-parameters, capture and evaluation, and without
+population-based training (tests/test_gpu_gat3_population.py).
 """
 from __future__ import annotations
 
@@ -39,9 +45,10 @@ from typing import Sequence
 import torch
 
 from . import _lib
-from ._lib import CTRL, SwarmActOut, SwarmAdamCfg, SwarmConfig, SwarmPopActor, SwarmPopMember, call, ptr, size
-from .engine import (CONVS, GRAPHS, HP_FIELDS, NETS, SwarmEngine, capture_ticks, check_hp_values, decode_ctrl,
-                     norm_flags)
+from ._lib import (CTRL, SwarmActOut, SwarmAdamCfg, SwarmConfig, SwarmGat3Member, SwarmPopActor, SwarmPopMember, call,
+                   ptr, size)
+from .engine import (CONVS, GRAPHS, HP_FIELDS, NETS, SwarmEngine, SwarmGat3Engine, capture_ticks, check_hp_values,
+                     decode_ctrl, norm_flags)
 
 
 def _bytes_of(struct) -> bytes:
@@ -130,9 +137,17 @@ def _is_real(v) -> bool:
     return isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v)
 
 
-class SwarmPopulation:
+class _Population:
+    """What ``SwarmPopulation`` (the one-layer network's fused tick) and ``SwarmGat3Population`` (the
+    three-layer network's unfused tick) share: members that are ordinary engines of ``member_class``
+    with one configuration, their control blocks and trainer outputs as rows of [P, ...] tensors, the
+    descriptor tables and the optimizer row table in device memory, and everything that needs no
+    more than those.  A subclass gives ``member_class``, ``_check_member``, ``_table`` and
+    ``train_tick``, and may re-home more buffers (``_rehome_more``)."""
+    member_class = SwarmEngine
+
     def __init__(self, seeds: Sequence[int], **engine_kwargs):
-        """``seeds`` plus the keyword arguments of ``SwarmEngine`` (everything but ``seed``); the
+        """``seeds`` plus the keyword arguments of the member engine (everything but ``seed``); the
         optimizer's (``engine.HP_FIELDS``) may each be a sequence of one value per member
         (``member_hp_kwargs``)."""
         seeds = list(seeds)
@@ -145,11 +160,11 @@ class SwarmPopulation:
         if engine_kwargs.get("world_size", 1) > 1 or engine_kwargs.get("peer") is not None:
             raise ValueError("a population runs on one GPU: no world_size > 1, no peer exchange")
         per_member = member_hp_kwargs(len(seeds), engine_kwargs)
-        self._adopt([SwarmEngine(seed=s, **kw) for s, kw in zip(seeds, per_member)])
+        self._adopt([self.member_class(seed=s, **kw) for s, kw in zip(seeds, per_member)])
 
     @classmethod
-    def from_engines(cls, engines: Sequence[SwarmEngine]) -> "SwarmPopulation":
-        """A population of engines that exist already (PopulationTrainer re-homes its trainers'
+    def from_engines(cls, engines: Sequence[SwarmEngine]):
+        """A population of engines that exist already (a population trainer re-homes its trainers'
         engines this way).  They must agree in everything but the seed and the optimizer's
         per-member hyper-parameters: one configuration, batch, ring capacity and device."""
         self = cls.__new__(cls)
@@ -171,9 +186,7 @@ class SwarmPopulation:
         for e in members:
             if e.world_size > 1 or e.peer is not None:
                 raise ValueError("a population runs on one GPU: no world_size > 1, no peer exchange")
-            if not e.fused:
-                raise ValueError("a population needs a configuration the fused training tick covers "
-                                 "(a learner, n_agents <= 16, net='gcn', a complete, kNN or radius graph)")
+            self._check_member(e)
             if shared(e) != shared(first):
                 raise ValueError("the members of a population share one configuration (all but the seed), one "
                                  "batch size and one ring capacity")
@@ -188,18 +201,16 @@ class SwarmPopulation:
         self.hp: SwarmAdamCfg = _copy_of(first.hp)
         dev = self.device
         f32 = dict(dtype=torch.float32, device=dev)
-        # every member's control block, reward, avg_dist, hits and hand-off workspace as rows of
-        # one tensor each; the members' attributes become views of their rows
+        # every member's control block, reward, avg_dist and hits (and what _rehome_more adds) as
+        # rows of one tensor each; the members' attributes become views of their rows
         self.ctrl = torch.stack([e.ctrl for e in members])                      # [P, 32] int32
         self.reward = torch.stack([e.reward for e in members])                  # [P, B, N]
         self.avg_dist = torch.stack([e.avg_dist for e in members])              # [P, B]
         self.hits = torch.stack([e.hits for e in members])                      # [P, B]
-        nb = first.tick_ws.numel()
-        self.tick_ws = torch.zeros(P, -(-nb // 512) * 512, dtype=torch.uint8, device=dev)
         for m, e in enumerate(members):
-            self.tick_ws[m, :nb].copy_(e.tick_ws)
             e.ctrl, e.reward, e.avg_dist, e.hits = self.ctrl[m], self.reward[m], self.avg_dist[m], self.hits[m]
-            e.tick_ws = self.tick_ws[m, :nb]
+        self._rehome_more()
+        for e in members:
             e.bind_outputs()
         # the descriptor tables in device memory, written once: one per output set of train_tick
         self._table_full = self._table(lambda e: e.out)
@@ -215,6 +226,13 @@ class SwarmPopulation:
         self.parent = torch.arange(P, dtype=torch.int32, device=dev)
         self._hp_stale = False
 
+    def _check_member(self, e):
+        """raise ValueError unless engine e can be a member"""
+        raise NotImplementedError
+
+    def _rehome_more(self):
+        """re-home what the subclass's tick needs besides ctrl, reward, avg_dist and hits"""
+
     @staticmethod
     def _row(e) -> SwarmAdamCfg:
         r = _copy_of(e.hp)
@@ -223,6 +241,107 @@ class SwarmPopulation:
 
     def _rows_differ(self) -> bool:
         return len({_bytes_of(self._row(e)) for e in self.members}) > 1
+
+    def set_member_hp(self, m: int, **fields):
+        """Change member m's optimizer hyper-parameters (``engine.HP_FIELDS``) for the ticks that
+        follow: ``members[m].set_hp(**fields)`` (so the member's own ``flush`` agrees) plus row m of
+        the device table, and ``per_member_hp`` becomes True if the rows now differ.  It means what
+        ``SwarmEngine.set_hp`` between two eager ticks means for a lone engine, bit for bit (a new
+        lr acts one optimizer step later, see there).  The table is read on every launch, so a
+        hipGraph captured while ``per_member_hp`` was True sees the new row at its next replay; one
+        captured while it was False holds the shared hp as a kernel argument and does not (set
+        ``per_member_hp = True`` before capturing a population whose rows will change)."""
+        if not 0 <= m < self.P:
+            raise ValueError(f"member {m} of {self.P}")
+        if self._hp_stale:   # the row is rewritten whole from the member's host hp
+            self.sync_hp()
+        e = self.members[m]
+        e.set_hp(**fields)   # validates
+        row = torch.frombuffer(bytearray(_bytes_of(self._row(e))), dtype=torch.uint8)
+        self._hp_table[m].copy_(row)   # on the current stream: behind every tick issued so far
+        if m == 0:   # the shared hp follows member 0, as at adoption (all there is when the rows are equal)
+            flags = self.hp.flags
+            self.hp = _copy_of(e.hp)
+            self.hp.flags = flags
+        self.per_member_hp = self.per_member_hp or self._rows_differ()
+
+    def reset(self, episode=None):
+        """Reset every member's environments (one small launch per member, once per episode)."""
+        for e in self.members:
+            e.reset(episode)
+
+    def set_eps(self, eps):
+        """Exploration epsilon of the next ticks: one value for all members, or one per member [P]."""
+        col = self.ctrl.view(torch.float32)[:, CTRL["eps"]]
+        if isinstance(eps, (int, float)):
+            col.fill_(float(eps))
+        else:
+            e = torch.as_tensor(eps, dtype=torch.float32).reshape(-1)
+            if e.numel() != self.P:
+                raise ValueError(f"set_eps: {e.numel()} values for {self.P} members")
+            col.copy_(e.to(self.device))
+
+    def capture(self, n_ticks: int, fn=None):
+        """Capture n_ticks calls of ``fn`` (default train_tick) into one hipGraph, on one stream."""
+        return capture_ticks(self.device, n_ticks, fn or self.train_tick)
+
+    # ------------------------------------------------------------------ reading back
+    def read_ctrl(self) -> list:
+        """Every member's control block as SwarmEngine.read_ctrl gives it; one device read."""
+        c = self.ctrl.cpu()
+        return [decode_ctrl(c[m]) for m in range(self.P)]
+
+    # ------------------------------------------------------------------ evaluation
+    def evaluate(self, n_envs: int, n_ticks: int, *, seed: int, episode: int = 0, graph=None, knn_k=None,
+                 eps: float = 0.0):
+        """A rollout (greedy while ``eps`` is 0) of every member's current weights on ``n_envs``
+        evaluation environments, the same for every member: one reset keyed (``seed``,
+        ``episode``) whose start is copied to every member's row of an evaluation state buffer,
+        then one swarm_pop_rollout launch.  ``graph`` / ``knn_k``: the evaluation graph (default the
+        training graph's).  Returns ``ActorPopulation.rollout``'s dict ([P, ...] device tensors,
+        the population's own buffers: the next evaluation of the same shape overwrites them).
+
+        It reads ``members[m].params`` as they stand, with no ``flush``: after a tick's two
+        launches that row holds the weights the tick acted with, and a pending optimizer step
+        stays pending.  It writes only its own state and output buffers (built once per shape), so
+        the training run keeps every bit: control blocks, replay rings, env states, Philox streams.
+        Row m equals ``evaluation_engine(members[m].cfg, ...)``'s lone reset + rollout."""
+        key = (n_envs, graph, knn_k)
+        ev = self._evals.get(key)
+        if ev is None:
+            cfg = evaluation_config(self.cfg, n_envs, graph, knn_k)
+            nst = max(size(self.lib, "swarm_state_floats", cfg), 1)
+            ev = self._evals[key] = (_PopRollout(self.lib, self.device, cfg, self.P),
+                                     torch.zeros(nst, dtype=torch.float32, device=self.device),
+                                     torch.zeros(self.P, nst, dtype=torch.float32, device=self.device))
+        roll, start, states = ev
+        roll.cfg.seed = seed & 0xFFFFFFFFFFFFFFFF
+        call(self.lib, "swarm_env_reset", roll.cfg, ptr(start), episode)
+        states.copy_(start.expand_as(states))
+        res = roll.prepare(n_ticks, [roll.cfg.seed] * self.P, [ptr(e.params) for e in self.members],
+                           [ptr(states[m]) for m in range(self.P)], 0, eps, False)
+        roll.launch(n_ticks)
+        return res
+
+
+class SwarmPopulation(_Population):
+    """P independent learners of the one-layer network ticked together by the fused tick (the module
+    docstring): two launches per tick, population-based training on the device."""
+    member_class = SwarmEngine
+
+    def _check_member(self, e):
+        if not e.fused:
+            raise ValueError("a population needs a configuration the fused training tick covers "
+                             "(a learner, n_agents <= 16, net='gcn', a complete, kNN or radius graph); "
+                             "SwarmGat3Engine learners (net='gat3') form a SwarmGat3Population")
+
+    def _rehome_more(self):
+        """every member's hand-off workspace as a row of one tensor"""
+        nb = self.members[0].tick_ws.numel()
+        self.tick_ws = torch.zeros(self.P, -(-nb // 512) * 512, dtype=torch.uint8, device=self.device)
+        for m, e in enumerate(self.members):
+            self.tick_ws[m, :nb].copy_(e.tick_ws)
+            e.tick_ws = self.tick_ws[m, :nb]
 
     def _table(self, out_of) -> torch.Tensor:
         arr = (SwarmPopMember * self.P)()
@@ -251,29 +370,6 @@ class SwarmPopulation:
             for e in self.members:
                 e._grad_dirty = False   # the reduce below rewrites grad and its partials
         call(self.lib, "swarm_pop_reduce_advance" + sfx, self.cfg, self.hp, *hp_table, ptr(table), self.P)
-
-    def set_member_hp(self, m: int, **fields):
-        """Change member m's optimizer hyper-parameters (``engine.HP_FIELDS``) for the ticks that
-        follow: ``members[m].set_hp(**fields)`` (so the member's own ``flush`` agrees) plus row m of
-        the device table, and ``per_member_hp`` becomes True if the rows now differ.  It means what
-        ``SwarmEngine.set_hp`` between two eager ticks means for a lone engine, bit for bit (a new
-        lr acts one optimizer step later, see there).  The table is read on every launch, so a
-        hipGraph captured while ``per_member_hp`` was True sees the new row at its next replay; one
-        captured while it was False holds the shared hp as a kernel argument and does not (set
-        ``per_member_hp = True`` before capturing a population whose rows will change)."""
-        if not 0 <= m < self.P:
-            raise ValueError(f"member {m} of {self.P}")
-        if self._hp_stale:   # the row is rewritten whole from the member's host hp
-            self.sync_hp()
-        e = self.members[m]
-        e.set_hp(**fields)   # validates
-        row = torch.frombuffer(bytearray(_bytes_of(self._row(e))), dtype=torch.uint8)
-        self._hp_table[m].copy_(row)   # on the current stream: behind every tick issued so far
-        if m == 0:   # the shared hp follows member 0, as at adoption (all there is when the rows are equal)
-            flags = self.hp.flags
-            self.hp = _copy_of(e.hp)
-            self.hp.flags = flags
-        self.per_member_hp = self.per_member_hp or self._rows_differ()
 
     # ------------------------------------------------------------------ population-based training
     def exploit(self, score, *, round: int, seed: int = 0, frac: float = 0.25, perturb=(0.8, 1.2), fields=("lr",),
@@ -323,22 +419,6 @@ class SwarmPopulation:
         _take_row(self.hp, self.members[0].hp)
         self._hp_stale = False
 
-    def reset(self, episode=None):
-        """Reset every member's environments (one small launch per member, once per episode)."""
-        for e in self.members:
-            e.reset(episode)
-
-    def set_eps(self, eps):
-        """Exploration epsilon of the next ticks: one value for all members, or one per member [P]."""
-        col = self.ctrl.view(torch.float32)[:, CTRL["eps"]]
-        if isinstance(eps, (int, float)):
-            col.fill_(float(eps))
-        else:
-            e = torch.as_tensor(eps, dtype=torch.float32).reshape(-1)
-            if e.numel() != self.P:
-                raise ValueError(f"set_eps: {e.numel()} values for {self.P} members")
-            col.copy_(e.to(self.device))
-
     def flush(self):
         """Apply every member's pending optimizer step (one small launch per member)."""
         if self._hp_stale:   # swarm_adam_flush takes each member's host hp
@@ -346,11 +426,7 @@ class SwarmPopulation:
         for e in self.members:
             e.flush()
 
-    def capture(self, n_ticks: int, fn=None):
-        """Capture n_ticks calls of ``fn`` (default train_tick) into one hipGraph, on one stream."""
-        return capture_ticks(self.device, n_ticks, fn or self.train_tick)
-
-    # ------------------------------------------------------------------ reading back
+    # ------------------------------------------------------------------ hand-offs
     def handoff_errors(self) -> list:
         """Every member's count of hand-off waits that hit their bound (all 0 in a correct run);
         one device read."""
@@ -363,42 +439,63 @@ class SwarmPopulation:
             raise RuntimeError(f"population tick: hand-off wait(s) overran their bound (member: count) {bad}; the "
                                "graphs they waited for were dropped from their TD batches")
 
-    def read_ctrl(self) -> list:
-        """Every member's control block as SwarmEngine.read_ctrl gives it; one device read."""
-        c = self.ctrl.cpu()
-        return [decode_ctrl(c[m]) for m in range(self.P)]
 
-    # ------------------------------------------------------------------ evaluation
-    def evaluate(self, n_envs: int, n_ticks: int, *, seed: int, episode: int = 0, graph=None, knn_k=None,
-                 eps: float = 0.0):
-        """A rollout (greedy while ``eps`` is 0) of every member's current weights on ``n_envs``
-        evaluation environments, the same for every member: one reset keyed (``seed``,
-        ``episode``) whose start is copied to every member's row of an evaluation state buffer,
-        then one swarm_pop_rollout launch.  ``graph`` / ``knn_k``: the evaluation graph (default the
-        training graph's).  Returns ``ActorPopulation.rollout``'s dict ([P, ...] device tensors,
-        the population's own buffers: the next evaluation of the same shape overwrites them).
+class SwarmGat3Population(_Population):
+    """P independent learners of the three-layer GAT (``SwarmGat3Engine``s, ``net="gat3"``: the
+    reference's Flocking experiment, ten seeds of one environment each) ticked together: the four
+    launches of ``SwarmGat3Engine.train_tick``, each once for all members,
 
-        It reads ``members[m].params`` as they stand, with no ``flush``: after a tick's two
-        launches that row holds the weights the tick acted with, and a pending optimizer step
-        stays pending.  It writes only its own state and output buffers (built once per shape), so
-        the training run keeps every bit: control blocks, replay rings, env states, Philox streams.
-        Row m equals ``evaluation_engine(members[m].cfg, ...)``'s lone reset + rollout."""
-        key = (n_envs, graph, knn_k)
-        ev = self._evals.get(key)
-        if ev is None:
-            cfg = evaluation_config(self.cfg, n_envs, graph, knn_k)
-            nst = max(size(self.lib, "swarm_state_floats", cfg), 1)
-            ev = self._evals[key] = (_PopRollout(self.lib, self.device, cfg, self.P),
-                                     torch.zeros(nst, dtype=torch.float32, device=self.device),
-                                     torch.zeros(self.P, nst, dtype=torch.float32, device=self.device))
-        roll, start, states = ev
-        roll.cfg.seed = seed & 0xFFFFFFFFFFFFFFFF
-        call(self.lib, "swarm_env_reset", roll.cfg, ptr(start), episode)
-        states.copy_(start.expand_as(states))
-        res = roll.prepare(n_ticks, [roll.cfg.seed] * self.P, [ptr(e.params) for e in self.members],
-                           [ptr(states[m]) for m in range(self.P)], 0, eps, False)
-        roll.launch(n_ticks)
-        return res
+        swarm_pop_gat3_act_step   grid (ceil(B / 4), P)                                     (1 launch)
+        swarm_pop_gat3_td_grad    grid (TD blocks of the batch, P), then the slab sum (26, P) (2 launches)
+        swarm_pop_gat3_adam_step  grid (1, P)                                               (1 launch)
+
+    ``SwarmGat3Population(seeds=[...], **kw)`` takes ``SwarmGat3Engine``'s keyword arguments, the
+    optimizer's one value for all or one per member; ``from_engines`` adopts existing engines.
+    ``pop.members[m]`` stays an ordinary ``SwarmGat3Engine``.  Member m computes bit for bit what a
+    lone ``SwarmGat3Engine`` with its seed computes with ``train_tick``
+    (tests/test_gpu_gat3_population.py).  ``set_member_hp``, ``per_member_hp``, ``reset``,
+    ``set_eps``, ``capture``, ``read_ctrl`` and ``evaluate`` are ``SwarmPopulation``'s.  The optimizer
+    step is applied at once, so ``flush`` does nothing; there is no population-based training and
+    no hand-off (``exploit``, ``handoff_errors``, ``check_handoffs`` raise ValueError)."""
+    member_class = SwarmGat3Engine
+
+    def _check_member(self, e):
+        if not isinstance(e, SwarmGat3Engine):
+            raise ValueError("a SwarmGat3Population is made of SwarmGat3Engine learners (net='gat3'); SwarmEngine "
+                             "learners form a SwarmPopulation")
+
+    def _table(self, out_of) -> torch.Tensor:
+        arr = (SwarmGat3Member * self.P)()
+        for m, e in enumerate(self.members):
+            arr[m] = SwarmGat3Member(e.cfg.seed, ptr(e.state), e.replay, ptr(e.params), ptr(e.target), ptr(e.adam_m),
+                                     ptr(e.adam_v), ptr(e.grad), ptr(e.ctrl), out_of(e), ptr(e.slabs), ptr(e.samples))
+        host = torch.frombuffer(bytearray(_bytes_of(arr)), dtype=torch.uint8)
+        return host.to(self.device)
+
+    def train_tick(self, full_out: bool = False):
+        """One training tick of every member: four launches.  Each member's TD batch indices go to
+        its ``samples``; with full_out its Q, actions and obs are written too.
+
+        While ``per_member_hp`` is False (all rows equal) the shared hp is a kernel argument;
+        otherwise the TD and optimizer launches read each member's row of the device table."""
+        table = ptr(self._table_full if full_out else self._table_min)
+        hp_table = ptr(self._hp_table) if self.per_member_hp else None
+        call(self.lib, "swarm_pop_gat3_act_step", self.cfg, table, self.P)
+        call(self.lib, "swarm_pop_gat3_td_grad", self.cfg, self.hp, hp_table, table, self.P)
+        call(self.lib, "swarm_pop_gat3_adam_step", self.cfg, self.hp, hp_table, table, self.P)
+
+    def flush(self):
+        """Nothing is ever pending: every tick applies its optimizer step at once."""
+
+    def exploit(self, *args, **kw):
+        raise ValueError("SwarmGat3Population has no population-based training: swarm_pop_exploit works on "
+                         "swarm_pop_member tables (the one-layer network's SwarmPopulation)")
+
+    def _no_handoff(self, *args, **kw):
+        raise ValueError("SwarmGat3Population ticks unfused (act, TD gradient, optimizer step): there is no fused "
+                         "tick and so no hand-off to count")
+
+    handoff_errors = check_handoffs = _no_handoff
 
 
 def evaluation_config(cfg: SwarmConfig, n_envs: int, graph=None, knn_k=None) -> SwarmConfig:

@@ -264,8 +264,9 @@ int swarm_gat3_q_backward(const swarm_config* cfg, const float* params, const fl
 /* ---- The learner of SWARM_NET_GAT3 on the unfused device path (train_gcn_dqn.py:112-137 for the
  * three-layer network): per tick swarm_act_step (with the replay) -> swarm_gat3_td_grad ->
  * swarm_gat3_adam_step, four launches, what swarm_act_step -> swarm_td_grad -> swarm_grad_reduce ->
- * swarm_adam_step is for the one-layer network.  The fused tick, populations and world_size > 1 stay
- * that network's.
+ * swarm_adam_step is for the one-layer network.  The fused tick, swarm_pop_member populations (PBT
+ * among them) and world_size > 1 stay that network's; populations of these learners are ticked by
+ * swarm_pop_gat3_act_step / _td_grad / _adam_step (below, after swarm_pop_rollout).
  *
  * swarm_gat3_td_grad: TD-loss gradient of a batch, the TD kernel + the slab sum, two launches.
  * Batch position i takes graph sample_in[i] (clamped to capacity * n_envs - 1) or, with sample_in
@@ -506,6 +507,68 @@ typedef struct swarm_pop_actor {
  * entry point cannot look into: valid pointers are the caller's contract. */
 int swarm_pop_rollout(const swarm_config* cfg, const swarm_pop_actor* actors, int32_t n_actors,
                       int32_t n_ticks, void* stream);
+
+/* ---- Populations of SWARM_NET_GAT3 learners: n_members >= 1 independent learners of the
+ * three-layer network ticked together (the reference's Flocking experiment: ten seeds, one
+ * environment each, batch 32, one after another, train_gcn_dqn.py:262-290), in the four launches
+ * per tick that one of them costs with swarm_act_step -> swarm_gat3_td_grad -> swarm_gat3_adam_step.
+ * All members share one swarm_config except the seed (cfg->seed is not used: each member's own keys
+ * its Philox streams and its replay sampling) and hp->batch.  Each member owns the rest, named by
+ * one descriptor: what the three lone entry points take.  The caller keeps an array of n_members
+ * descriptors in DEVICE memory; the kernels read it on every launch, so a descriptor rewritten
+ * between two launches holds from the next launch on, the next replay of a captured hipGraph
+ * included.  Members never exchange data and must not share a buffer: member m computes bit for
+ * bit what a lone learner with cfg->seed = members[m].seed computes with the three lone entry
+ * points (tests/test_gpu_gat3_population.py). */
+typedef struct swarm_gat3_member {
+  uint64_t seed;          /* the member's Philox key (what swarm_config.seed is to a lone learner) */
+  float* state;           /* swarm_state_floats(cfg) floats                                        */
+  swarm_replay replay;    /* the member's ring; replay.capacity is the member's own                */
+  float* params;          /* SWARM_GAT3_GRAD_FLOATS floats each: 409 weights (swarm_gat3_adam_step) */
+  float* target;
+  float* adam_m;
+  float* adam_v;
+  float* grad;            /* as swarm_gat3_td_grad's grad                                          */
+  swarm_ctrl* ctrl;
+  swarm_act_out out;      /* any pointer may be NULL                                               */
+  float* slabs;           /* swarm_td_workspace_floats(cfg, hp->batch) floats                      */
+  int32_t* sample_out;    /* [hp->batch] this tick's TD batch indices, or NULL                     */
+} swarm_gat3_member;
+
+/* swarm_act_step for every member in ONE launch, grid (ceil(n_envs / 4), n_members): block (x, m)
+ * does for member m what block x of swarm_act_step does with the member's seed, params, state,
+ * replay (the push included; a NULL replay.s pushes nothing), ctrl and out.
+ * Checks, in this order, all before any launch: a NULL cfg or members, or n_members outside
+ * 1..65535: SWARM_E_BADARG; then every configuration returns what swarm_act_step returns for it
+ * (SWARM_E_BADARG / SWARM_E_KNN_K; GAT3 with GCNConv: SWARM_E_BADARG); net != SWARM_NET_GAT3:
+ * SWARM_E_UNSUPPORTED; n_envs = 0 returns 0 and launches nothing. */
+int swarm_pop_gat3_act_step(const swarm_config* cfg, const swarm_gat3_member* members, int32_t n_members,
+                            void* stream);
+/* swarm_gat3_td_grad for every member in TWO launches: the TD kernel with grid (slabs of the batch,
+ * n_members), then the slab sum with grid (26, n_members); block (x, m) does what block x of the
+ * lone launch does with member m's params, target, replay, ctrl, slabs, grad and sample_out.  The
+ * batch is always drawn in-kernel, member m's seed in the sampling key (there is no sample_in); the
+ * skip rule (fewer than `batch` graphs in the ring: grad = 0) is each member's own, from its ctrl.
+ * swarm_pop_gat3_adam_step: swarm_gat3_adam_step for every member in ONE launch, grid (1,
+ * n_members), the ring capacity from members[m].replay.capacity.
+ * member_hp: NULL (every member runs *hp), or an array of n_members swarm_adam_cfg in DEVICE memory,
+ * read on every launch like `members`: member m then takes from row m what
+ * swarm_pop_train_tick_hp's members take (lr, beta1, beta2, eps, max_norm, gamma,
+ * update_target_every, lr_d, beta1_d, beta2_d; gamma acts in the TD launch, the rest in the
+ * optimizer's), while batch, world_size and flags stay *hp's and the rows' are IGNORED.  Valid rows
+ * (update_target_every >= 1, finite values) are the caller's contract, as valid descriptors are.
+ * With all rows equal to *hp both ways compute the same bits.
+ * Checks of both, in this order, all before any launch: a NULL cfg, hp or members, or n_members
+ * outside 1..65535: SWARM_E_BADARG; then the configuration and hp return what swarm_gat3_td_grad
+ * returns for them (SWARM_E_BADARG / SWARM_E_KNN_K; GAT3 with GCNConv: SWARM_E_BADARG; net !=
+ * SWARM_NET_GAT3: SWARM_E_UNSUPPORTED; hp->world_size != 1: SWARM_E_UNSUPPORTED; SWARM_GRAPH_DENSE:
+ * SWARM_E_BADARG).  The descriptors are device memory the entry points cannot look into: valid
+ * pointers are the caller's contract.  No atomics, no allocation, no host sync: bitwise
+ * reproducible, capturable.  (tests/test_gat3_population_host.py) */
+int swarm_pop_gat3_td_grad(const swarm_config* cfg, const swarm_adam_cfg* hp, const swarm_adam_cfg* member_hp,
+                           const swarm_gat3_member* members, int32_t n_members, void* stream);
+int swarm_pop_gat3_adam_step(const swarm_config* cfg, const swarm_adam_cfg* hp, const swarm_adam_cfg* member_hp,
+                             const swarm_gat3_member* members, int32_t n_members, void* stream);
 
 /* ---- Population-based training (Jaderberg et al. 2017): exploit and explore on the device.  The
  * reference trains every seed under fixed hyper-parameters and never moves a learner

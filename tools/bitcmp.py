@@ -10,11 +10,15 @@ leave every bit alone).  The kinds of case:
   td   : the unfused swarm_td_grad on a seeded replay (tests/test_gpu_parity.py _fill_replay) and a
          fixed sample_in; the gradient buffer;
   qb   : swarm_q_backward on a case of tests/test_q_backward.py; the whole gradient buffer;
-  g3b  : swarm_gat3_q_backward on a case of tests/test_gat3_backward.py; its 416-float gradient buffer.
+  g3b  : swarm_gat3_q_backward on a case of tests/test_gat3_backward.py; its 416-float gradient buffer;
+  g3t  : a SwarmGat3Engine (swarm_act_step, swarm_gat3_td_grad, swarm_gat3_adam_step) runs `ticks` training
+         ticks; the gradient and the batch indices after every tick and the final weights, Adam moments,
+         target, ring, state and control block.
 
 usage: python tools/bitcmp.py LIB_A LIB_B [scenario N B ticks]    one tick case (LIB = base or a path)
-       python tools/bitcmp.py LIB_A LIB_B --matrix [OUT.jsonl]    MATRIX: every instance of the TD
-           kernel, the fused tick and q_backward at its smallest size, then the benchmark's sizes
+       python tools/bitcmp.py LIB_A LIB_B --matrix [OUT.jsonl] [--kinds=g3t,g3b]   MATRIX: every instance of
+           the TD kernel, the fused tick and q_backward at its smallest size, then the benchmark's sizes
+           (--kinds: only its cases of these kinds)
 Exit status 1 when a case differs or a run counted a hand-off error.
 """
 import json
@@ -25,7 +29,8 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-# (kind, ...): tick: scenario, N, envs, ticks, graph, conv; td: scenario, N, S, graph, k, conv; qb, g3b: case index
+# (kind, ...): tick: scenario, N, envs, ticks, graph, conv; td: scenario, N, S, graph, k, conv; qb, g3b: case index;
+# g3t: N, envs, batch, ring, ticks, graph, k
 MATRIX = (
     [("tick", scen, N, B, 6, "complete", conv)
      for scen, N, B in (("GoTo", 5, 64),                 # two 8-slot graphs per wave, padded slots
@@ -37,6 +42,9 @@ MATRIX = (
     + [("td", "ObstacleAvoidance", 12, 5, "knn", 5, "gat")]
     + [("qb", i) for i in range(17)]
     + [("g3b", i) for i in range(13)]                    # every slot class, graph kind and the two-slab reduce groups
+    # the three-layer GAT's learner: every slot class and graph kind, skipped ticks, a wrapping ring
+    + [("g3t", 5, 2, 7, 8, 10, "complete", 0), ("g3t", 12, 5, 5, 10, 8, "knn", 5), ("g3t", 17, 2, 3, 4, 6, "radius", 0),
+       ("g3t", 10, 1, 32, 1000, 36, "complete", 0)]
     + [("tick", scen, N, B, 6, "complete", "gat")        # the benchmark's sizes
        for scen, N, B in (("GoTo", 8, 1024), ("ObstacleAvoidance", 12, 1024), ("ObstacleAvoidance", 5, 512),
                           ("ObstacleAvoidance", 12, 512))]
@@ -82,6 +90,21 @@ def run_case(case):
         eng.td_grad(sample_in=idx.cuda())
         torch.cuda.synchronize()
         return {"grad": eng.grad.cpu()}, eng.handoff_errors()
+    if kind == "g3t":
+        _, N, B, S, ring, T, graph, k = case
+        eng = swarm_amd.SwarmGat3Engine("Flocking", N, B, seed=3, batch=S, eps=0.3, replay_capacity=ring,
+                                        update_target_every=3, graph=graph, knn_k=max(k, 1), radius=0.5)
+        eng.reset(0)
+        grads, samples = [], []
+        for t in range(T):
+            eng.train_tick(full_out=True)
+            grads.append(eng.grad.clone())
+            samples.append(eng.samples.clone())
+        torch.cuda.synchronize()
+        assert eng.read_ctrl()["adam_step"] >= 1
+        out = {k: getattr(eng, k).cpu() for k in ("params", "adam_m", "adam_v", "target", "rep_s", "rep_s1", "rep_r",
+                                                  "rep_a", "_state_buf", "ctrl", "q")}
+        return dict(out, grad=torch.stack(grads).cpu(), samples=torch.stack(samples).cpu()), 0
     if kind == "g3b":
         from tests import test_gat3_backward as T
         N, B, graph, k, seed, holes = T.CASES[case[1]]
@@ -128,8 +151,12 @@ def main():
         return child(sys.argv[2], [tuple(c) for c in json.loads(sys.argv[3])])
     a, b = sys.argv[1], sys.argv[2]
     log = None
+    kinds = [x[len("--kinds="):].split(",") for x in sys.argv if x.startswith("--kinds=")]
+    sys.argv = [x for x in sys.argv if not x.startswith("--kinds=")]
     if len(sys.argv) > 3 and sys.argv[3] == "--matrix":
         cases, log = MATRIX, sys.argv[4] if len(sys.argv) > 4 else None
+        if kinds:
+            cases = [c for c in MATRIX if c[0] in kinds[0]]
     else:
         scen = sys.argv[3] if len(sys.argv) > 3 else "GoTo"
         N = int(sys.argv[4]) if len(sys.argv) > 4 else 8

@@ -35,7 +35,15 @@ P learners that have trained for 40 ticks, frac = 0.25, lr and gamma perturbed, 
 Same method: HIP events around back-to-back rounds, the ways alternating, medians with min and max,
 in us per round.  Default sizes 10,64.
 
-usage: python tools/pop_time.py [--rollout | --pbt] [--repeats 7] [--sizes 1,10,64] [--out population_time.json]
+``--gat3`` times the three-layer GAT's learners at the reference's Flocking shape (10 agents, 1 env,
+batch 32, the default ring, 100-tick episodes), P learners (seeds 0..P-1):
+  sequential : P lone SwarmGat3Engines, each replaying its own captured 100-tick episode (4 launches
+               per tick), one after another on one stream;
+  population : one SwarmGat3Population replaying one captured 100-tick episode of all P members (the
+               same 4 launches per tick, the member as the grid's second dimension).
+Same method as the default mode; us per population tick.  Default output profiles/gat3_pop_time.json.
+
+usage: python tools/pop_time.py [--rollout | --pbt | --gat3] [--repeats 7] [--sizes 1,10,64] [--out population_time.json]
 Prints one JSON line per configuration and population size.
 """
 import argparse
@@ -164,6 +172,45 @@ def measure_rollout(scen, N, P, repeats, n_envs=8, knn_k=5):
     return out
 
 
+def measure_gat3(scen, N, P, repeats):
+    kw = dict(scenario=scen, n_agents=N, n_envs=1, batch=32, eps=0.05, shared_reset=True)
+    lone = [swarm_amd.SwarmGat3Engine(seed=s, **kw) for s in range(P)]
+    pop = swarm_amd.SwarmGat3Population(seeds=list(range(P)), **kw)
+    assert not pop.per_member_hp
+    for e in lone:
+        e.reset(0)
+    pop.reset(0)
+    lone_graphs = [e.capture(TICKS) for e in lone]
+    pop_graph = pop.capture(TICKS)
+
+    def sequential():
+        for g in lone_graphs:
+            g.replay()
+
+    ways = {"sequential": sequential, "population": pop_graph.replay}
+    # enough episodes per window that it lasts tens of milliseconds at least
+    episodes = {"sequential": max(2, math.ceil(40 / P)), "population": 40}
+    for k, fn in ways.items():   # warm-up: code objects loaded, rings past the batch size, clocks up
+        window_us(fn, 2)
+    times = {k: [] for k in ways}
+    for _ in range(repeats):
+        for k, fn in ways.items():
+            times[k].append(window_us(fn, episodes[k]))
+    torch.cuda.synchronize()
+    ctrl = pop.read_ctrl() + [e.read_ctrl() for e in lone]
+    assert min(c["adam_step"] for c in ctrl) > 0, "the timed ticks did not train"
+    assert all(math.isfinite(c["loss"]) for c in ctrl)
+    out = {"mode": "gat3", "scenario": scen, "n_agents": N, "n_envs": 1, "batch": 32, "population": P,
+           "ticks_per_episode": TICKS, "launches_per_tick": {"sequential": 4 * P, "population": 4},
+           "episodes_per_window": episodes, "repeats": repeats, "build": pop.lib.swarm_build_info().decode()}
+    for k, v in times.items():
+        out[k + "_us_per_tick"] = round(statistics.median(v), 3)
+        out[k + "_us_min_max"] = [round(min(v), 3), round(max(v), 3)]
+    out["sequential_over_population"] = round(out["sequential_us_per_tick"] / out["population_us_per_tick"], 3)
+    out["slowest_population_beats_fastest_sequential"] = max(times["population"]) < min(times["sequential"])
+    return out
+
+
 PBT_ROUNDS = 50
 PBT_CTRL_WORDS = [3, 5, 6, 7, 10, 11, 12, 13, 14, 15, 24, 25]   # what swarm_pop_exploit copies of swarm_ctrl
 
@@ -248,6 +295,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--rollout", action="store_true", help="time evaluation rollouts instead of training ticks")
     ap.add_argument("--pbt", action="store_true", help="time one PBT round: swarm_pop_exploit against host copies")
+    ap.add_argument("--gat3", action="store_true", help="time SwarmGat3Population against lone SwarmGat3Engines")
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--sizes", default=None, help="population sizes (default 1,10,64; --pbt: 10,64)")
     ap.add_argument("--configs", default=None, help="e.g. GoTo:5,ObstacleAvoidance:10 (default: all four)")
@@ -256,7 +304,11 @@ def main():
     a.sizes = a.sizes or ("10,64" if a.pbt else "1,10,64")
     if a.pbt and not a.configs:
         a.configs = "GoTo:5"
-    fn = measure_pbt if a.pbt else measure_rollout if a.rollout else measure
+    if a.gat3:
+        a.configs = a.configs or "Flocking:10"
+        a.out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                      "gat3_pop_time.json")
+    fn = measure_gat3 if a.gat3 else measure_pbt if a.pbt else measure_rollout if a.rollout else measure
     configs = CONFIGS if not a.configs else tuple((c.split(":")[0], int(c.split(":")[1])) for c in a.configs.split(","))
     rows = []
     for scen, N in configs:
