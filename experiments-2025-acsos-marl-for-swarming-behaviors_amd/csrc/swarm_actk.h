@@ -66,8 +66,11 @@ struct ActSmem {
 // vb / nvb: this block's index among the nvb acting blocks of the launch (the fused
 // training-tick kernel runs acting blocks beside TD blocks).
 // HO: fused-tick hand-off publishing (swarm_tick.hip only).  NET: SWARM_NET_GCN (the D-layout
-// MFMA forward) or SWARM_NET_GAT3 (swarm_gat3.h; acting only, no learner prologue)
-template <int NS, int MODE, int SCEN, int SPEC, bool HO = false, int NET = SWARM_NET_GCN>
+// MFMA forward) or SWARM_NET_GAT3 (swarm_gat3.h; acting only, no learner prologue).
+// FRAG: the forward's weight-image operands read in one batch behind the image's barrier
+// (swarm_dl.h DFrag; about 60 VGPRs through the forward, so a kernel takes it only where its
+// occupancy stays)
+template <int NS, int MODE, int SCEN, int SPEC, bool HO = false, int NET = SWARM_NET_GCN, bool FRAG = false>
 __device__ __forceinline__ void act_body(ActSmem<NS>& S, const int vb, const int nvb,
                                          const swarm_ctrl* __restrict__ ctrl, float* state, const float* grad,
                                          const float* w_cur, const float* m_cur, const float* v_cur, int B, int N,
@@ -359,6 +362,9 @@ __device__ __forceinline__ void act_body(ActSmem<NS>& S, const int vb, const int
   }
   __syncthreads();   // weight image complete
   const float* P = Pw;
+  static_assert(!FRAG || (MODE == MODE_TICK && NET == SWARM_NET_GCN), "fragments: the training tick's forward");
+  DFrag<NS> wfrag;
+  if constexpr (FRAG) wfrag.load(P, c, p);
   SWARM_STAMP(1);
 
   const int n_ticks = (MODE == MODE_ROLLOUT) ? A.n_ticks : 1;
@@ -381,7 +387,9 @@ __device__ __forceinline__ void act_body(ActSmem<NS>& S, const int vb, const int
     if (MODE != MODE_STEP && NET == SWARM_NET_GAT3) {
       gat3_forward<NS>(P, d, N, graph, A.k, A.radius, A.dense, V, F);
     } else if (MODE != MODE_STEP) {
-      if constexpr (kDefer) dl_forward<NS, 8, NS, spec_complete_graph(SPEC)>(P, d, N, graph, A.k, A.radius, conv, A.dense, V, false, F, deferred0);
+      if constexpr (FRAG && kDefer) dl_forward<NS, 8, NS, spec_complete_graph(SPEC), true>(P, d, N, graph, A.k, A.radius, conv, A.dense, V, false, F, deferred0, &wfrag);
+      else if constexpr (FRAG) dl_forward<NS, 8, NS, spec_complete_graph(SPEC), true>(P, d, N, graph, A.k, A.radius, conv, A.dense, V, false, F, DlNoHook(), &wfrag);
+      else if constexpr (kDefer) dl_forward<NS, 8, NS, spec_complete_graph(SPEC)>(P, d, N, graph, A.k, A.radius, conv, A.dense, V, false, F, deferred0);
       else dl_forward<NS, 8, NS, spec_complete_graph(SPEC)>(P, d, N, graph, A.k, A.radius, conv, A.dense, V, false, F);
     }
     if constexpr (kDefer) {   // the deferred work's branches: pairs in contact, an exploring env

@@ -15,6 +15,7 @@
 // GCN.forward: src/training/train_gcn_dqn.py:59-70 (GATConv -> tanh -> lin1 -> relu
 // -> lin2); GATConv math: PyG 2.5.3 (heads 1, add_self_loops False).
 #pragma once
+#include <cstddef>
 #include <type_traits>
 
 #include "swarm_wpg.h"
@@ -459,6 +460,95 @@ __device__ inline void knn_masks_wave(int lane, int N, int k, WSmall<NS>& sm, fl
 #endif
 }
 
+// Every weight-image operand of one forward, as registers of lane (c, p).  None depends on the
+// state, only on the image and the lane, so a caller whose image is complete long before its
+// state (dl_forward's FRAG switch) reads them in one batch with load(): the forward then holds
+// no LDS round trip of the image between its MFMA chains, and its Q epilogue is one 16-B store.
+// Masks are selects on registers after the reads, never a branch around a read; clamps keep
+// every read inside the image (a word that is selected away may hold anything, pad included).
+template <int NS>
+struct DFrag {
+  float a0[2][2];       // conv1.lin: W[16 t + c][p], W[16 t + c][4 + p] (0 for 4 + p >= kFeat)
+  float as[2][4];       // att_src[16 t + 4 p + r]
+  float ad[2][4];       // att_dst
+  float bias[2][4];     // conv bias
+  float a1[2][2][4];    // [out tile t2][k tile t][r] = W1[16 t2 + c][16 t + 4 p + r]
+  float b1v[2][4];
+  float a2[2][4];       // W2[c][16 t + 4 p + r] (0 for c >= kActions)
+  float b2[4];          // b2[4 p + r] (0 for 4 p + r >= kActions)
+
+  static constexpr int ix_a0(int t, int c, int p, int hi) { return L_W + (16 * t + c) * kFeat + 4 * hi + p; }
+  static constexpr int ix_vec(int base, int t, int p) { return base + 16 * t + 4 * p; }   // 4 words from here
+  static constexpr int ix_a1(int t2, int t, int c, int p) { return L_W1 + (16 * t2 + c) * kWRow + 16 * t + 4 * p; }
+  static constexpr int ix_a2(int t, int c, int p) {
+    return L_W2 + (c < kActions ? c : kActions - 1) * kWRow + 16 * t + 4 * p;
+  }
+  static constexpr int ix_b2(int p) { return L_B2 + 4 * (p < 3 ? p : 2); }
+  static constexpr bool ok1(int i) { return i >= 0 && i < N_LDS_PARAMS; }
+  static constexpr bool ok4(int i) { return i >= 0 && i + 3 < N_LDS_PARAMS && i % 4 == 0; }   // one 16-B read
+  // every word that load() reads lies inside the image, for every lane
+  static constexpr bool in_image() {
+    for (int c = 0; c < 16; ++c)
+      for (int p = 0; p < 4; ++p) {
+        if (!ok4(ix_b2(p))) return false;
+        for (int t = 0; t < 2; ++t) {
+          if (!ok1(ix_a0(t, c, p, 0)) || !ok1(ix_a0(t, c, p, 1))) return false;
+          if (!ok4(ix_vec(L_ATT_SRC, t, p)) || !ok4(ix_vec(L_ATT_DST, t, p)) || !ok4(ix_vec(L_BIAS, t, p)) ||
+              !ok4(ix_vec(L_B1, t, p)))
+            return false;
+          if (!ok4(ix_a2(t, c, p)) || !ok4(ix_a1(0, t, c, p)) || !ok4(ix_a1(1, t, c, p))) return false;
+        }
+      }
+    return true;
+  }
+
+  static __device__ __forceinline__ void rd4(const float* __restrict__ P, int i, float x[4]) {
+    const float4 w = *reinterpret_cast<const float4*>(P + i);
+    x[0] = w.x; x[1] = w.y; x[2] = w.z; x[3] = w.w;
+  }
+  static __device__ __forceinline__ float4 f4(const float x[4]) { return make_float4(x[0], x[1], x[2], x[3]); }
+  static __device__ __forceinline__ void pin4(float x[4]) {
+    asm volatile("" : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]));
+  }
+  // all reads issued together, pinned where they land (the compiler would otherwise sink each
+  // read back in front of its first use), masks after
+  __device__ __forceinline__ void load(const float* __restrict__ P, int c, int p) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      a0[t][0] = P[ix_a0(t, c, p, 0)];
+      a0[t][1] = P[ix_a0(t, c, p, 1)];
+      rd4(P, ix_vec(L_ATT_SRC, t, p), as[t]);
+      rd4(P, ix_vec(L_ATT_DST, t, p), ad[t]);
+      rd4(P, ix_vec(L_BIAS, t, p), bias[t]);
+#pragma unroll
+      for (int t2 = 0; t2 < 2; ++t2) rd4(P, ix_a1(t2, t, c, p), a1[t2][t]);
+      rd4(P, ix_vec(L_B1, t, p), b1v[t]);
+      rd4(P, ix_a2(t, c, p), a2[t]);
+    }
+    rd4(P, ix_b2(p), b2);
+    asm volatile("" : "+v"(a0[0][0]), "+v"(a0[0][1]), "+v"(a0[1][0]), "+v"(a0[1][1]));
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      pin4(as[t]); pin4(ad[t]); pin4(bias[t]); pin4(a1[0][t]); pin4(a1[1][t]); pin4(b1v[t]); pin4(a2[t]);
+    }
+    pin4(b2);
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      a0[t][1] = (4 + p < kFeat) ? a0[t][1] : 0.0f;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) a2[t][r] = (c < kActions) ? a2[t][r] : 0.0f;
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) b2[r] = (4 * p + r < kActions) ? b2[r] : 0.0f;
+    // the masked values pinned as well: left to the compiler, each select is formed again
+    // between the MFMAs of the chain that reads it
+    asm volatile("" : "+v"(a0[0][1]), "+v"(a0[1][1]));
+    pin4(a2[0]); pin4(a2[1]); pin4(b2);
+  }
+};
+static_assert(DFrag<8>::in_image() && DFrag<16>::in_image() && DFrag<32>::in_image(),
+              "DFrag::load reads words (16-B aligned where it reads four) of the weight image only");
+
 // Full GCN.forward.  F.x must hold the lane's features (zero for nodes >= N).  P is the
 // padded LDS weight image.  Writes the H rows (and T / R rows if keep_tr) of V, the
 // per-node scalars of V.sm, and leaves F.t / F.zr / F.cc / F.cr / F.q for the backward.
@@ -472,10 +562,13 @@ struct DlNoHook {
 // UNIT: the graph is the complete graph at compile time (SPEC_COMPLETE_*): its 0 / 1 multiplicity
 // is carried as a predicate.  A kernel with a runtime graph keeps the m form for every graph
 // (the same bits on the complete graph, complete_mult), so each kernel holds one form only.
-template <int NS, int SB = -1, int GS = NS, bool UNIT = false, class HOOK = DlNoHook>
+// FRAG: *fragp holds the caller's fragments of P (DFrag::load, issued where the image is complete
+// and the state is not yet); else each operand is read in front of its use.  Either way the
+// operand lands in the same local, and one code path does the arithmetic.
+template <int NS, int SB = -1, int GS = NS, bool UNIT = false, bool FRAG = false, class HOOK = DlNoHook>
 __device__ inline void dl_forward(const float* __restrict__ P, const DGeom<NS>& d, int N, int graph, int k, float radius, int conv,
                                   const uint8_t* __restrict__ dense, const WView<NS>& V, bool keep_tr, DFwd<NS>& F,
-                                  const HOOK& hook = HOOK()) {
+                                  const HOOK& hook = HOOK(), const DFrag<NS>* fragp = nullptr) {
 #define DF_STAMP(i) do { if (SB >= 0) SWARM_STAMP(SB + (i)); } while (0)
   constexpr int CT = DGeom<NS>::CT;
   WSmall<NS>& sm = *V.sm;
@@ -486,12 +579,17 @@ __device__ inline void dl_forward(const float* __restrict__ P, const DGeom<NS>& 
     float a0[2][2];
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-      a0[t][0] = P[L_W + (16 * t + c) * kFeat + p];
-      // read unconditionally (p = 3 reads the next row's first weight, inside the image) and
-      // masked after: no branch around a masked LDS read at the head of every forward
-      a0[t][1] = P[L_W + (16 * t + c) * kFeat + 4 + p];
-      asm volatile("" : "+v"(a0[t][1]));
-      a0[t][1] = (4 + p < kFeat) ? a0[t][1] : 0.0f;
+      if constexpr (FRAG) {
+        a0[t][0] = fragp->a0[t][0];
+        a0[t][1] = fragp->a0[t][1];
+      } else {
+        a0[t][0] = P[L_W + (16 * t + c) * kFeat + p];
+        // read unconditionally (p = 3 reads the next row's first weight, inside the image) and
+        // masked after: no branch around a masked LDS read at the head of every forward
+        a0[t][1] = P[L_W + (16 * t + c) * kFeat + 4 + p];
+        asm volatile("" : "+v"(a0[t][1]));
+        a0[t][1] = (4 + p < kFeat) ? a0[t][1] : 0.0f;
+      }
     }
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct)
@@ -507,10 +605,16 @@ __device__ inline void dl_forward(const float* __restrict__ P, const DGeom<NS>& 
   // ---- attention scores (h * att).sum(-1): 8 features per lane, then the 4 row groups
   float ssrc[CT];
   {
-    const float4 s0 = *reinterpret_cast<const float4*>(P + L_ATT_SRC + 4 * p);
-    const float4 s1 = *reinterpret_cast<const float4*>(P + L_ATT_SRC + 16 + 4 * p);
-    const float4 d0 = *reinterpret_cast<const float4*>(P + L_ATT_DST + 4 * p);
-    const float4 d1 = *reinterpret_cast<const float4*>(P + L_ATT_DST + 16 + 4 * p);
+    float4 s0, s1, d0, d1;
+    if constexpr (FRAG) {
+      s0 = DFrag<NS>::f4(fragp->as[0]); s1 = DFrag<NS>::f4(fragp->as[1]);
+      d0 = DFrag<NS>::f4(fragp->ad[0]); d1 = DFrag<NS>::f4(fragp->ad[1]);
+    } else {
+      s0 = *reinterpret_cast<const float4*>(P + L_ATT_SRC + 4 * p);
+      s1 = *reinterpret_cast<const float4*>(P + L_ATT_SRC + 16 + 4 * p);
+      d0 = *reinterpret_cast<const float4*>(P + L_ATT_DST + 4 * p);
+      d1 = *reinterpret_cast<const float4*>(P + L_ATT_DST + 16 + 4 * p);
+    }
     const float as[2][4] = {{s0.x, s0.y, s0.z, s0.w}, {s1.x, s1.y, s1.z, s1.w}};
     const float ad[2][4] = {{d0.x, d0.y, d0.z, d0.w}, {d1.x, d1.y, d1.z, d1.w}};
 #pragma unroll
@@ -673,8 +777,13 @@ __device__ inline void dl_forward(const float* __restrict__ P, const DGeom<NS>& 
     for (int t = 0; t < 2; ++t)
 #pragma unroll
       for (int ks = 0; ks < NS / 4; ++ks) ah[t][ks] = V.H[4 * ks + p][16 * t + c];
-    const float4 b0 = *reinterpret_cast<const float4*>(P + L_BIAS + 4 * p);
-    const float4 b1 = *reinterpret_cast<const float4*>(P + L_BIAS + 16 + 4 * p);
+    float4 b0, b1;
+    if constexpr (FRAG) {
+      b0 = DFrag<NS>::f4(fragp->bias[0]); b1 = DFrag<NS>::f4(fragp->bias[1]);
+    } else {
+      b0 = *reinterpret_cast<const float4*>(P + L_BIAS + 4 * p);
+      b1 = *reinterpret_cast<const float4*>(P + L_BIAS + 16 + 4 * p);
+    }
     const float bias[2][4] = {{b0.x, b0.y, b0.z, b0.w}, {b1.x, b1.y, b1.z, b1.w}};
     // every column tile's chains first (each keeps its k order), then the epilogues: the T-row
     // store's test does not stand between two tiles' MFMAs
@@ -712,11 +821,18 @@ __device__ inline void dl_forward(const float* __restrict__ P, const DGeom<NS>& 
     for (int t2 = 0; t2 < 2; ++t2)
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
-        const float4 w = *reinterpret_cast<const float4*>(P + L_W1 + (16 * t2 + c) * kWRow + 16 * t + 4 * p);
+        float4 w;
+        if constexpr (FRAG) w = DFrag<NS>::f4(fragp->a1[t2][t]);
+        else w = *reinterpret_cast<const float4*>(P + L_W1 + (16 * t2 + c) * kWRow + 16 * t + 4 * p);
         a1[t2][t][0] = w.x; a1[t2][t][1] = w.y; a1[t2][t][2] = w.z; a1[t2][t][3] = w.w;
       }
-    const float4 bb0 = *reinterpret_cast<const float4*>(P + L_B1 + 4 * p);
-    const float4 bb1 = *reinterpret_cast<const float4*>(P + L_B1 + 16 + 4 * p);
+    float4 bb0, bb1;
+    if constexpr (FRAG) {
+      bb0 = DFrag<NS>::f4(fragp->b1v[0]); bb1 = DFrag<NS>::f4(fragp->b1v[1]);
+    } else {
+      bb0 = *reinterpret_cast<const float4*>(P + L_B1 + 4 * p);
+      bb1 = *reinterpret_cast<const float4*>(P + L_B1 + 16 + 4 * p);
+    }
     const float b1v[2][4] = {{bb0.x, bb0.y, bb0.z, bb0.w}, {bb1.x, bb1.y, bb1.z, bb1.w}};
     hook();
 #pragma unroll
@@ -752,7 +868,11 @@ __device__ inline void dl_forward(const float* __restrict__ P, const DGeom<NS>& 
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       float4 w = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (c < kActions) w = *reinterpret_cast<const float4*>(P + L_W2 + c * kWRow + 16 * t + 4 * p);
+      if constexpr (FRAG) {
+        w = DFrag<NS>::f4(fragp->a2[t]);
+      } else {
+        if (c < kActions) w = *reinterpret_cast<const float4*>(P + L_W2 + c * kWRow + 16 * t + 4 * p);
+      }
       a2[t][0] = w.x; a2[t][1] = w.y; a2[t][2] = w.z; a2[t][3] = w.w;
     }
 #pragma unroll
@@ -763,7 +883,16 @@ __device__ inline void dl_forward(const float* __restrict__ P, const DGeom<NS>& 
 #pragma unroll
         for (int r = 0; r < 4; ++r) qa = mfma16(a2[t][r], F.zr[ct][t][r], qa);
       const int n = 16 * ct + c;
-      if (n < NS && p < 3) {
+      if constexpr (FRAG) {
+        // one 16-B store per lane: row words 9..11 are padding that nothing reads.  The row piece
+        // is 16-B aligned: Q leads WSmall, rows and the struct are 16-B multiples, and every
+        // WSmall stands at a 16-B multiple of its block's LDS (as the read-back below assumes too)
+        static_assert(offsetof(WSmall<NS>, Q) == 0 && sizeof(sm.Q[0]) % 16 == 0 && sizeof(WSmall<NS>) % 16 == 0,
+                      "Q rows of a 16-B aligned WSmall are 16-B aligned");
+        if (n < NS && p < 3)
+          *static_cast<float4*>(__builtin_assume_aligned(&sm.Q[n][4 * p], 16)) =
+              make_float4(qa[0] + fragp->b2[0], qa[1] + fragp->b2[1], qa[2] + fragp->b2[2], qa[3] + fragp->b2[3]);
+      } else if (n < NS && p < 3) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int a = 4 * p + r;

@@ -113,7 +113,9 @@ __device__ inline void drop_overrun(const bool (&okc)[DGeom<NS>::CT], bool (&dro
     if (bad[ct]) { drop[ct] = true; nv[ct] = false; }
 }
 
-template <int NS, int GS, int SPEC, bool FUSED = false>   // SPEC: graph + conv fixed at compile time (swarm_common.h)
+// FRAG: both forwards' weight-image operands read in one batch right behind B0 (swarm_dl.h DFrag),
+// so a wave that waits for a hand-off holds them long before its state lands
+template <int NS, int GS, int SPEC, bool FUSED = false, bool FRAG = false>   // SPEC: graph + conv fixed at compile time (swarm_common.h)
 __device__ __forceinline__ void td_body(TdSmem<NS>& L, const int vb, const int32_t* sample_in, const float* rs,
                                         const float* rs_next, const float* rr, const uint8_t* ra, int S, int B,
                                         int N, int capacity, const TdArgs& A, const TdFused& X,
@@ -298,6 +300,8 @@ __device__ __forceinline__ void td_body(TdSmem<NS>& L, const int vb, const int32
     for (int ct = 0; ct < CT; ++ct) TB.tdrop[row0 + 16 * ct + c] = 0;
   }
   __syncthreads();   // B0: weight images
+  DFrag<NS> wfrag;
+  if constexpr (FRAG) wfrag.load(online ? Pon : Ptg, c, p);
   SWARM_STAMP(2);
   bool pre = false;
 #pragma unroll
@@ -362,7 +366,11 @@ __device__ __forceinline__ void td_body(TdSmem<NS>& L, const int vb, const int32
   // ---- forwards: online on s (activations kept), target on s' (train_gcn_dqn.py:119-121).
   //      Everything after B1 waits for the target waves' y, so they issue first.
   if (!online && !waited) __builtin_amdgcn_s_setprio(2);
-  dl_forward<NS, 16, GS, spec_complete_graph(SPEC)>(online ? Pon : Ptg, d, N, graph, A.k, A.radius, conv, nullptr, V, online, F);
+  if constexpr (FRAG)
+    dl_forward<NS, 16, GS, spec_complete_graph(SPEC), true>(online ? Pon : Ptg, d, N, graph, A.k, A.radius, conv, nullptr, V, online,
+                                                            F, DlNoHook(), &wfrag);
+  else
+    dl_forward<NS, 16, GS, spec_complete_graph(SPEC)>(online ? Pon : Ptg, d, N, graph, A.k, A.radius, conv, nullptr, V, online, F);
   // fused: the rest of this tick's transitions, each as late as its first use: a for the online
   // waves' pre path here; r (published after the acting wave's reward) by the online waves after
   // it, in their wait for the target waves' y, so no poll sits between the target forward and B1

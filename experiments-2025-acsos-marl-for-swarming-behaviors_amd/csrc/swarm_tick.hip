@@ -39,11 +39,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GS == 8 ? 2
   // dwords); the acting/TD split is derived from B instead of a 15th kernel argument
   const int n_act = (B + kActWPB - 1) / kActWPB;
   if ((int)blockIdx.x < n_act) {
-    act_body<NSA, MODE_TICK, SCEN, SPEC, true, SWARM_NET_GCN>(U.a, blockIdx.x, n_act, ctrl, state, grad, w_cur, m_cur,
-                                                              v_cur, B, N, A);
+    act_body<NSA, MODE_TICK, SCEN, SPEC, true, SWARM_NET_GCN, true>(U.a, blockIdx.x, n_act, ctrl, state, grad, w_cur,
+                                                                    m_cur, v_cur, B, N, A);
   } else {
-    td_body<NST, GS, SPEC, true>(U.t, (int)blockIdx.x - n_act, nullptr, T.replay.s, T.replay.s_next, T.replay.r,
-                                      T.replay.a, T.S, B, N, T.replay.capacity, T, X, ctrl, grad, w_cur, m_cur, v_cur);
+    td_body<NST, GS, SPEC, true, true>(U.t, (int)blockIdx.x - n_act, nullptr, T.replay.s, T.replay.s_next, T.replay.r,
+                                       T.replay.a, T.S, B, N, T.replay.capacity, T, X, ctrl, grad, w_cur, m_cur, v_cur);
   }
 }
 
